@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: train images/sec of the ssUnet-GAN G+D step on synthetic 3x512x512 tiles.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 runs one rank per GPU over RCCL.  Either the caller starts the ranks
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`: RANK/WORLD_SIZE are in the
@@ -11,9 +11,17 @@ WORLD_SIZE differs from --gpus, or whose backend is not RCCL ("nccl") without SS
 
 One "step" = one pass of the hot path (train_seg_gan.py:182-233: G fwd+bwd, 3x D fwd+bwd, two
 clip+Adam updates) over one batch of 16 tiles per GPU already resident in HBM.  Prints ONE JSON
-line (rank 0) with the whole-job images/sec, the MFMA roofline of the dominant kernel measured
-with HIP events on the launch stream during the timed steps, and (N=1 only) a bounded CPU
-baseline: the oracle's plain-torch step timed on this box's host cores.
+line (rank 0) with the whole-job images/sec and ms_per_step of the K timed steps.  A plain run does
+nothing else: set up, W warm-up steps, K timed steps, the outputs (--dump-outputs), the line.
+
+--full adds everything else the line used to carry: the MFMA roofline of the dominant kernel
+measured with HIP events on the launch stream during the timed steps, the encoder-3x3 / HBM-stage /
+all-reduce sub-metrics, the fp32-MFMA reference steps, the measured ceilings of the device, the side
+legs for BASELINE configs 4 / 5 and, for N=1, a bounded CPU baseline: the oracle's plain-torch step
+timed on this box's host cores.
+
+--dump-outputs DIR writes what the last timed step computed (dump_outputs) as DIR/<name>.npy; the
+inputs and the initial models are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -188,8 +196,8 @@ def side_configs(S, dev, note):
     if os.environ.get('SSG_DIST_FORCE') != '1' and not _under_profiler():
         try:
             env = dict(os.environ, SSG_DIST_FORCE='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(_free_port()))
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-fp32-reference',
-                                '--no-side-configs'], env=env, capture_output=True, text=True, timeout=240)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline',
+                                '--no-fp32-reference', '--no-side-configs'], env=env, capture_output=True, text=True, timeout=240)
             line = next((json.loads(l) for l in r.stdout.splitlines() if l.startswith('{')), None)
             if line is None:
                 out['dp_costs'] = {'error': 'child exited %d: %s' % (r.returncode, r.stderr[-300:])}
@@ -306,6 +314,29 @@ def bucket_allreduce_ms(syncs, dev, reps=5):
     return out
 
 
+DUMP_NAMES = ('loss', 'iou', 'dice', 'closs', 'adv_g', 'adv_d')     # gan_step's return values, in order
+DUMP_SAMPLE = 1 << 22                                               # parameter values sampled per model: 16 MB of fp32
+
+
+def dump_outputs(path, out, models):
+    """--dump-outputs: what the last timed step computed, as float32 DIR/<name>.npy (about 32 MB in all).  The six scalars
+    gan_step returns, and the state the step leaves in the models: every floating buffer (batch-norm running statistics) and a
+    fixed, seeded sample of DUMP_SAMPLE parameter values per model (the same indices in every run and build)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in zip(DUMP_NAMES, out)}
+    for name, m in models:
+        flat = torch.cat([p.detach().reshape(-1) for p in m.parameters()])
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(1234)).sort().values
+            flat = flat[idx.to(flat.device)]
+        arrays[name + '_params_sample'] = flat.float().cpu().numpy()
+        arrays[name + '_buffers'] = torch.cat([b.detach().reshape(-1).float() for b in m.buffers() if b.is_floating_point()]).cpu().numpy()
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), v)
+    return sum(v.nbytes for v in arrays.values())
+
+
 def launch_check(args):
     """--launch-check: the launcher / rendezvous / rank bookkeeping of an N-rank run WITHOUT the GPU step (CPU rehearsal over
     gloo: tests/test_bench_launch.py).  Prints the same JSON skeleton with value null."""
@@ -338,10 +369,15 @@ def main():
     ap.add_argument('--no-fp32-reference', action='store_true', help='skip the extra steps with every conv on the fp32 MFMA')
     ap.add_argument('--launch-check', action='store_true', help='rendezvous only, no GPU step (CPU rehearsal of the N-rank launch)')
     ap.add_argument('--no-side-configs', action='store_true', help='skip the short legs for BASELINE configs 4 / 5 and the world-1 RCCL cost run')
+    ap.add_argument('--full', action='store_true', help='also the roofline, sub-metrics, fp32-MFMA reference, measured ceilings, side legs '
+                                                        'and CPU baseline (the --no-* options apply to this)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy')
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1:
+        raise SystemExit('--steps must be >= 1')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # Not started by a launcher: start the ranks ourselves.  Nothing above this line has touched HIP
         # (importing torch does not), and the child is a new process, not an exec of this one.
@@ -403,7 +439,8 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    S.ops.PROFILE = []; S.ops.PROFILE_HBM = []; S.ops.PROFILE_COMM = []
+    if args.full:                                                  # HIP events around the launches: only --full reports them
+        S.ops.PROFILE = []; S.ops.PROFILE_HBM = []; S.ops.PROFILE_COMM = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step()
@@ -411,13 +448,16 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    prof, S.ops.PROFILE = S.ops.PROFILE, None
-    prof_hbm, S.ops.PROFILE_HBM = S.ops.PROFILE_HBM, None
-    prof_comm, S.ops.PROFILE_COMM = S.ops.PROFILE_COMM, None
+    prof, S.ops.PROFILE = S.ops.PROFILE or [], None
+    prof_hbm, S.ops.PROFILE_HBM = S.ops.PROFILE_HBM or [], None
+    prof_comm, S.ops.PROFILE_COMM = S.ops.PROFILE_COMM or [], None
     note('timed %d steps: %.1f ms/step' % (args.steps, dt / args.steps * 1e3))
+    if args.dump_outputs and rank == 0:                           # before anything below steps the models again
+        nbytes = dump_outputs(args.dump_outputs, out, (('G', G), ('D', D)))
+        note('outputs of the last timed step: %.1f MB in %s' % (nbytes / 1e6, args.dump_outputs))
     # the same step with every conv on the fp32 MFMA (SSG_MFMA_SPLIT=0), measured in THIS run: 1 warm-up + a few timed steps
     ref32 = None
-    if S.ops.MFMA_SPLIT and not args.no_fp32_reference:
+    if args.full and S.ops.MFMA_SPLIT and not args.no_fp32_reference:
         S.ops.MFMA_SPLIT = False
         try:
             step()
@@ -443,7 +483,7 @@ def main():
         note('fp32-MFMA reference: %.1f ms/step' % ref32['ms_per_step'])
     devices = [torch.cuda.current_device()]
     buckets = None
-    if world == 1 and sync_g is not None:                  # SSG_DIST_FORCE=1: one rank, every collective through the backend
+    if args.full and world == 1 and sync_g is not None:    # SSG_DIST_FORCE=1: one rank, every collective through the backend
         buckets = bucket_allreduce_ms((('G', sync_g), ('D', sync_d)), dev)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -452,7 +492,8 @@ def main():
         ids = [None] * world
         dist.all_gather_object(ids, (rank, torch.cuda.current_device(), os.environ.get('LOCAL_RANK')))
         devices = [d for _, d, _ in sorted(ids)]
-        buckets = bucket_allreduce_ms((('G', sync_g), ('D', sync_d)), dev)
+        if args.full:
+            buckets = bucket_allreduce_ms((('G', sync_g), ('D', sync_d)), dev)
 
     if rank == 0:
         imgs = args.batch * world * args.steps
@@ -518,7 +559,7 @@ def main():
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
             'matrix_pipe': ('fp32 tensors and fp32 accumulation everywhere; the dense 3x3 unit-stride convs and input gradients multiply on the bf16 pipe with each '
                             'fp32 operand split into 3 bf16 terms (error vs fp64 = that of the fp32-MFMA kernel: tests/test_split_gpu.py; SSG_MFMA_SPLIT=0 '
-                            'runs them on v_mfma_f32_32x32x2_f32: `fp32_mfma_reference`)') if S.ops.MFMA_SPLIT else 'v_mfma_f32_32x32x2_f32 (fp32 MFMA) for every conv',
+                            'runs them on v_mfma_f32_32x32x2_f32: `fp32_mfma_reference` under --full)') if S.ops.MFMA_SPLIT else 'v_mfma_f32_32x32x2_f32 (fp32 MFMA) for every conv',
             'config': {'workload': 'UNet_R_SS_v2 generator + SRGAN-style discriminator, one G+D step (train_seg_gan.py:182-233), '
                                    '%d x 3x%dx%d tiles per GPU, fp32, Adam lr 2e-5' % (args.batch, args.size, args.size),
                        'global_batch': args.batch * world, 'tile': args.size,
@@ -526,8 +567,10 @@ def main():
                        'dead_d_param_grads_of_g_step': 'computed' if D_PASSES == 9 else 'not computed (zeroed unread in the reference, train_seg_gan.py:225)'},
             'backend': backend if backend else (dist.get_backend() if S.dp.is_dist() else None), 'devices': devices,
             'loss': round(float(out[0]), 6), 'iou': round(float(out[1]), 6), 'dice': round(float(out[2]), 6),
-            'roofline': roof,
+            'full': args.full,
         }
+        if args.full:
+            line['roofline'] = roof
         # north-star sub-metrics (BASELINE.json): MFMA roofline on the 3x3 encoder convs; achieved HBM rate on the memory-bound
         # stages -- algorithmic bytes of SURVEY.md 8(d) / HIP-event time on the launch stream, against the 8 TB/s spec
         if enc[2]:
@@ -554,15 +597,15 @@ def main():
             line['sync_bn_allreduce_ms'] = round(sum(v[1] for v in comm.values()) / args.steps, 3)
         if buckets is not None:
             line['grad_bucket_allreduce'] = buckets
-        if world == 1:
+        if args.full and world == 1:
             line['measured_ceilings'] = measured_ceilings(S, dev)
             # the split kernels against what the bf16 pipe of THIS device sustains on random operands (power-limited: DESIGN.md 3.9)
             if roof and roof.get('executed') and line['measured_ceilings'].get('mfma_bf16_random_operand_tflops'):
                 key = 'mfma_bf16_16x16x32_random_operand_tflops' if 'k32' in roof['kernel'] else 'mfma_bf16_random_operand_tflops'
                 roof['executed']['frac_of_measured_random_operand_rate'] = round(roof['executed']['achieved'] / line['measured_ceilings'][key], 4)
-        if world == 1 and not args.no_side_configs and os.environ.get('SSG_DIST_FORCE') != '1':
+        if args.full and world == 1 and not args.no_side_configs and os.environ.get('SSG_DIST_FORCE') != '1':
             line.update(side_configs(S, dev, note))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if dist.is_available() and dist.is_initialized():          # also the world-1 rehearsal under SSG_DIST_FORCE=1
