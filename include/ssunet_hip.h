@@ -109,8 +109,9 @@ typedef struct {
  * ABI 7 (round 4): ssg_conv2d_split_bn may also return 1128 or 1064 -- the launch goes to the 32-channel-chunk kernel on
  * v_mfma_f32_16x16x32_bf16 (conv_igemm_halo_k32.hip: 8 x 32-pixel x 128-channel tiles of 512 threads, or 4 x 32 x 64 of 256), whose
  * weights are packed by the same two functions with BN = that code: layout [R/bn][Kp/32 steps = chunk32 * 9 + tap][bn/16
- * fragments][3 planes][64 lanes][16 B] (bn = code - 1000; R % bn == 0, Kp % 288 == 0).  A third code, 2064 (16 x 32-pixel x 64-channel
- * tiles of 512 threads), reads the pack of 1064: pack with BN = 1064.  ssg_conv_set_k32_mode(0 / 1 / 2): never /
+ * fragments][3 planes][64 lanes][16 B] (bn = code - 1000; R % bn == 0, Kp % 288 == 0).  The value is always the pack format the
+ * launch reads, whichever kernel reads it (the 16 x 32-pixel x 64-channel tiles of 512 threads read the pack of 1064;
+ * ssg_conv2d_kernel_id tells the kernels apart).  ssg_conv_set_k32_mode(0 / 1 / 2): never /
  * where the grid fills the chip (default, SSG_K32) / wherever the shape is legal (tests). */
 int ssg_conv2d_split_bn(const ssg_conv_desc* d);
 int ssg_conv2d_in_affine_ok(const ssg_conv_desc* d);   /* ABI 8: 1 when the launch for `d` (w_split set) takes in_scale / in_shift */
@@ -130,11 +131,18 @@ int ssg_conv2d_igemm_f32(const ssg_conv_desc* d, void* stream);
  * unit strides (SPADE's C->3->h->C chain normalization.py:90-96, the 3-channel image / logit /
  * mask layers archs.py:210,615, models_seg_gan.py:37) run on HBM-bound VALU kernels; everything
  * else goes to the MFMA implicit GEMM above.  Same descriptor, same semantics.
- * ssg_conv2d_kernel_id: 0..2 = conv_igemm_kernel<128,128>/<256,64>/<256,32> (register-staged),
- * 30/31/32 = conv_igemm_halo_kernel<128,128>/<256,64>/<128,64> (LDS-resident halo tile: the default for the 9 taps of
- * a 3x3 window at unit stride), 33/34 = conv_igemm_halo16_kernel<128,128>/<128,64> (the same on 8x16-pixel tiles, images <= 16 wide), 20/21/22 = conv_igemm_dma_kernel<128,128>/<256,64>/<128,64> (LDS-DMA pipeline, the default for Cin % 16 == 0
- * and Cout > 32), 12/13 = thin4 kernels on the 4x4x1 MFMA (4-channel input / Cout <= 4 with Cin % 64 == 0),
- * 10 = thin small-Cout (VALU; profiling labels). */
+ * ssg_conv2d_kernel_id: the kernel ssg_conv2d_f32 launches for the descriptor as given (w_split, in_scale, bnpart and ws
+ * included; profiling labels):
+ *   0..2 = conv_igemm_kernel<128,128>/<256,64>/<256,32> (register-staged),
+ *   10 = thin small-Cout (VALU), 12/13 = thin4 kernels on the 4x4x1 MFMA (4-channel input / Cout <= 8 with Cin % 64 == 0),
+ *   14 = tiny4 (4 -> <= 8 channels, VALU), 15 = thin32 (4-channel input, 3x3, Cout >= 32 on the 32x32x2 MFMA),
+ *   16 = conv1x1_k64 (streaming 1x1, 64 input channels),
+ *   20/21/22 = conv_igemm_dma_kernel<128,128>/<256,64>/<128,64> (LDS-DMA pipeline, Cin % 16 == 0 and Cout > 32),
+ *   30/31/32 = conv_igemm_halo_kernel<128,128>/<256,64>/<128,64> (LDS-resident halo tile: the 9 taps of a 3x3 window at unit
+ *   stride), 33/34 = conv_igemm_halo16_kernel<128,128>/<128,64> (the same on 8x16-pixel tiles, images <= 16 wide),
+ *   split operands (w_split): 40/41 = conv_igemm_halo_x3_kernel<128,128>/<128,64>, 42 = the merged parity classes
+ *   (conv_igemm_halo_x3_kernel<128,64,4,1,true>), 50/51 = conv_igemm_dma_x3_kernel<64>/<128>,
+ *   60..64 = conv_halo_k32_kernel<8,128>/<4,64>/<16,64>/<8,16>/<8,32> (pack formats 1128 / 1064 / 1064 / 1016 / 1032). */
 int ssg_conv2d_f32(const ssg_conv_desc* d, void* stream);
 int ssg_conv2d_kernel_id(const ssg_conv_desc* d);
 /* Rows of `bnpart` the launch for `d` writes, or 0 when the kernel `d` maps to has no statistics epilogue (the caller then

@@ -223,7 +223,6 @@ int pick_variant(const ssg_conv_desc* d) {
 // register-staged kernel (A/B switch for measurements).
 ConvArgs to_args(const ssg_conv_desc* d);
 bool uses_halo(const ConvArgs& a);
-int split_bn(const ssg_conv_desc* d);
 
 bool uses_dma(const ssg_conv_desc* d) {
   static const int use_dma = [] { const char* e = getenv("SSG_IGEMM_DMA"); return e ? atoi(e) : 1; }();
@@ -299,162 +298,138 @@ ConvArgs to_args(const ssg_conv_desc* d) {
   return a;
 }
 
-// column tile (64 / 128; 1064 / 1128 = the k32 pack format of conv_igemm_halo_k32.hip) of the split-operand kernel for `d`, or 0: 3x3 unit-stride launches on the halo path that would not split K
-int split_bn(const ssg_conv_desc* d) {
-  if (d->Cout <= 32) {                                          // narrow k32 tiles (1016 / 1032), or nothing
-    if (d->kmode != 0 || d->parity_merge) return 0;
-    const ConvArgs a = to_args(d);
-    return uses_halo(a) ? ssg_conv_halo_k32_fmt(a) : 0;
+// The kernel families in the order the dispatcher tries them: thin VALU / 4x4x1 kernels and the streaming 1x1 kernel for the
+// few-channel shapes, then on the MFMA path the split-operand kernels (bf16 terms on the bf16 matrix pipe; only with w_split) and
+// the fp32 kernels (LDS halo tile, LDS-DMA pipeline, register-staged).
+enum ConvKind { KIND_THIN4, KIND_THIN, KIND_1X1, KIND_K32, KIND_PARITY, KIND_HALO_X3, KIND_DMA_X3, KIND_HALO, KIND_DMA, KIND_REG };
+
+struct ConvPlan {
+  int rc;            // validate(d); nothing below is set unless SSG_OK
+  ConvArgs a;        // kernel arguments of the descriptor as given (split-K and w_split applied by the launch)
+  ConvKind kind;
+  int variant;       // KIND_THIN4 / THIN: the thin kind; fp32 MFMA kinds: pick_variant (the kernel narrows it further)
+  int fmt;           // split-operand kernels: k32 format code 1016 / 1032 / 1064 / 1128 / 2064, or column tile 64 / 128
+  int pack;          // ssg_conv2d_split_bn: the split pack w_split must hold (fmt, with 2064 reading the pack of 1064), or 0
+  int th, tw;        // pixel tile of the statistics epilogue (a bnpart row per tile), th = 0: none
+  int ksplit;        // split-K slabs of the launch (1 = none): needs a workspace of ws_bytes
+  int64_t ws_bytes;  // ssg_conv2d_workspace_bytes
+  bool in_affine, bwd_stats;
+  int id;            // ssg_conv2d_kernel_id
+};
+
+// One decision per descriptor: which kernel ssg_conv2d_f32 launches (mfma_only: ssg_conv2d_igemm_f32, no thin kernels), and
+// everything the queries report about that launch.  Whether a family is eligible is decided in the family's file.
+ConvPlan plan_conv(const ssg_conv_desc* d, bool mfma_only = false) {
+  ConvPlan p{};
+  p.rc = validate(d);
+  if (p.rc != SSG_OK) return p;
+  p.ksplit = 1;
+  if (!mfma_only) {
+    if ((p.variant = ssg_thin4_conv_kind(d))) { p.kind = KIND_THIN4; p.id = ssg_thin4_conv_id(d, p.variant); return p; }
+    if ((p.variant = ssg_thin_conv_kind(d))) { p.kind = KIND_THIN; p.id = 9 + p.variant; return p; }
   }
-  if (!uses_dma(d)) return 0;
-  const ConvArgs a = to_args(d);
-  if (d->parity_merge) return ssg_conv_halo_x3_parity_ok(a) ? 64 : 0;
-  if (!uses_halo(a)) return ssg_conv_dma_x3_bn(a);            // 1x1, stride 2, parity-class launches: the LDS-DMA pipeline
-  if (!ssg_conv_halo_x3_ok(a, pick_variant(d))) return 0;
-  const int k32 = ssg_conv_halo_k32_fmt(a);                     // 1128 / 1064: the 32-channel-chunk kernel and its pack format (grids that fill the chip, or forced)
-  if (k32) return k32;
-  if (d->ldo % 4 == 0 && !((uintptr_t)d->out & 15) && ssg_conv_halo_ksplit(a, pick_variant(d)) > 1) return 0;   // small grids keep split-K
-  return ssg_conv_halo_x3_bn(a, pick_variant(d));
+  const ConvArgs& a = p.a = to_args(d);
+  const int v = p.variant = pick_variant(d);
+  const bool dma = uses_dma(d), halo = uses_halo(a);
+  // small grids split K over the idle CUs (fp32 halo tile, 16-byte output quads); never with bnpart (ssg_conv_halo_ksplit)
+  const int ksplit = dma && halo && d->ldo % 4 == 0 && !((uintptr_t)d->out & 15) ? ssg_conv_halo_ksplit(a, v) : 1;
+  if (d->Cout <= 32) p.fmt = halo ? ssg_conv_halo_k32_fmt(a) : 0;            // narrow k32 tiles (1016 / 1032), or nothing
+  else if (!dma) p.fmt = 0;
+  else if (d->parity_merge) p.fmt = ssg_conv_halo_x3_parity_ok(a) ? 64 : 0;
+  else if (!halo) p.fmt = ssg_conv_dma_x3_bn(a);                               // 1x1, stride 2, parity classes: LDS-DMA pipeline
+  else if (!ssg_conv_halo_x3_ok(a, v)) p.fmt = 0;
+  else if ((p.fmt = ssg_conv_halo_k32_fmt(a))) {}                              // 32-channel chunks (grids that fill the chip, or forced)
+  else p.fmt = ksplit > 1 ? 0 : ssg_conv_halo_x3_bn(a, v);                     // small grids keep split-K on the fp32 kernel
+  p.pack = p.fmt == 2064 ? 1064 : p.fmt;
+  if (d->w_split && p.fmt) p.kind = d->parity_merge ? KIND_PARITY : p.fmt >= 1000 ? KIND_K32 : halo ? KIND_HALO_X3 : KIND_DMA_X3;
+  else p.kind = !dma ? KIND_REG : halo ? KIND_HALO : KIND_DMA;
+  int hv, bn;
+  switch (p.kind) {
+    case KIND_K32:
+      ssg_conv_halo_k32_tile(p.fmt, &p.th, &p.tw);
+      p.id = p.fmt == 1128 ? 60 : p.fmt == 1064 ? 61 : p.fmt == 2064 ? 62 : p.fmt == 1016 ? 63 : 64;
+      break;
+    case KIND_PARITY:  p.th = 8; p.tw = 16; p.id = 42; break;
+    case KIND_HALO_X3: p.th = 4; p.tw = 32; p.id = p.fmt == 128 ? 40 : 41; break;
+    case KIND_DMA_X3:  p.th = 8; p.tw = 16; p.id = p.fmt == 128 ? 51 : 50; break;
+    case KIND_HALO:
+      hv = ssg_conv_halo_variant(a, v);
+      p.id = 30 + hv;
+      if (ksplit > 1) {
+        p.ws_bytes = (int64_t)ksplit * d->N * d->GH * d->GW * ((d->Cout + 3) & ~3) * (int64_t)sizeof(float);
+        if (d->ws && !d->bnpart && d->ws_bytes >= p.ws_bytes && !((uintptr_t)d->ws & 15)) p.ksplit = ksplit;
+      } else {
+        ssg_conv_halo_tile(hv, &p.th, &p.tw, &bn);
+      }
+      break;
+    case KIND_DMA:     p.th = ssg_conv_dma_variant(a, v) == 1 ? 16 : 8; p.tw = 16; p.id = 20 + ssg_conv_dma_variant(a, v); break;
+    default:           p.id = v; break;
+  }
+  p.in_affine = p.kind == KIND_K32 && ssg_conv_halo_k32_in_affine_ok(a, p.fmt);
+  p.bwd_stats = p.kind == KIND_K32 && !d->res && !d->bias && d->act == SSG_ACT_NONE && !d->in_scale && ssg_conv_halo_k32_bwd_stats_ok(a, p.fmt);
+  if (!mfma_only && ssg_conv1x1_k64_ok(d)) {     // the streaming kernel takes no bnpart: th / tw stay those of the kernel bnpart selects
+    p.kind = KIND_1X1; p.id = 16; p.pack = 0;
+  }
+  return p;
 }
 
+int launch_plan(const ssg_conv_desc* d, const ConvPlan& p, void* stream) {
+  if (p.rc != SSG_OK) return p.rc;
+  SSG_REQUIRE(!d->in_scale || (d->in_shift && p.in_affine), SSG_EINVAL,
+              "conv: in_scale on a descriptor whose kernel has no fused input transform (ssg_conv2d_in_affine_ok == 0)");
+  SSG_REQUIRE(!d->bwd_x || (d->bnpart && d->bwd_scale && d->bwd_shift && d->bwd_mean && p.bwd_stats), SSG_EINVAL,
+              "conv: bwd_x on a descriptor whose kernel has no backward-statistics epilogue (ssg_conv2d_bwd_stats_ok == 0), or without bnpart");
+  SSG_REQUIRE(!d->bnpart || p.th, SSG_EINVAL, "conv: bnpart given but this shape has no statistics epilogue (ssg_conv2d_bnpart_rows == 0)");
+  SSG_REQUIRE(!d->parity_merge || p.kind == KIND_PARITY, SSG_EINVAL,
+              "conv: parity_merge needs a descriptor for which ssg_conv2d_split_bn reports 64 and its w_split pack");
+  hipStream_t st = (hipStream_t)stream;
+  ConvArgs a = p.a;
+  switch (p.kind) {
+    case KIND_THIN4: return ssg_thin4_conv_launch(d, p.variant, st);
+    case KIND_THIN:  return ssg_thin_conv_launch(d, p.variant, st);
+    case KIND_1X1:   return ssg_conv1x1_k64_launch(d, st);
+    case KIND_HALO:
+      if (p.ksplit > 1) { a.ws = d->ws; a.ksplit = p.ksplit; }
+      return ssg_conv_igemm_halo_launch(a, p.variant, st);
+    case KIND_DMA:   return ssg_conv_igemm_dma_launch(a, p.variant, st);
+    case KIND_REG:
+      if (p.variant == 0) return launch<128, 128, 2, 2>(a, st);
+      if (p.variant == 1) return launch<256, 64, 4, 1>(a, st);
+      return launch<256, 32, 4, 1>(a, st);
+    default: break;
+  }
+  SSG_REQUIRE(ssg_aligned16(d->w_split), SSG_EALIGN, "conv: w_split alignment");
+  a.w = (const float*)d->w_split;                        // operands split into bf16 terms on the bf16 matrix pipe
+  switch (p.kind) {
+    case KIND_K32:     return ssg_conv_igemm_halo_k32_launch(a, p.fmt, st);
+    case KIND_PARITY:  return ssg_conv_igemm_halo_x3_parity_launch(a, st);
+    case KIND_HALO_X3: return ssg_conv_igemm_halo_x3_launch(a, p.variant, st);
+    default:           return ssg_conv_igemm_dma_x3_launch(a, st);
+  }
+}
 
 }  // namespace
 
-// rows of the batch-norm partial buffer the launch for `d` writes (one per M-tile), or 0 when the kernel `d` maps to has no
-// statistics epilogue (thin / register-staged kernels): the caller then runs ssg_bn_stats_f32 instead
+// The queries below read the plan of the descriptor as given (include/ssunet_hip.h).
+extern "C" int ssg_conv2d_split_bn(const ssg_conv_desc* d) { const ConvPlan p = plan_conv(d); return p.rc == SSG_OK ? p.pack : 0; }
+extern "C" int ssg_conv2d_in_affine_ok(const ssg_conv_desc* d) { const ConvPlan p = plan_conv(d); return p.rc == SSG_OK && p.in_affine; }
+extern "C" int ssg_conv2d_bwd_stats_ok(const ssg_conv_desc* d) { const ConvPlan p = plan_conv(d); return p.rc == SSG_OK && p.bwd_stats; }
+extern "C" int64_t ssg_conv2d_workspace_bytes(const ssg_conv_desc* d) { const ConvPlan p = plan_conv(d); return p.rc == SSG_OK ? p.ws_bytes : 0; }
+extern "C" int ssg_conv2d_kernel_id(const ssg_conv_desc* d) { const ConvPlan p = plan_conv(d); return p.rc == SSG_OK ? p.id : p.rc; }
+
+// rows of the batch-norm partial buffer the launch for `d` writes (one per pixel tile), or 0 when the kernel has no statistics
+// epilogue (thin / register-staged kernels, split-K launches): the caller then runs ssg_bn_stats_f32 instead
 extern "C" int ssg_conv2d_bnpart_rows(const ssg_conv_desc* d) {
-  if (!d || validate(d) != SSG_OK) return 0;
-  if (ssg_thin4_conv_kind(d) || ssg_thin_conv_kind(d)) return 0;
-  const bool narrow_k32 = d->Cout <= 32 && d->w_split && split_bn(d) >= 1000;
-  if (!uses_dma(d) && !narrow_k32) return 0;
-  const ConvArgs a = to_args(d);
-  int th, tw;
-  if (d->w_split && split_bn(d) > 0) {                          // split-operand kernels: 4 x 32-pixel halo tiles (also where fp32 takes <256,64>), 8 x 16 DMA tiles
-    if (split_bn(d) >= 1000) ssg_conv_halo_k32_tile(split_bn(d), &th, &tw);
-    else if (uses_halo(a)) { th = 4; tw = 32; } else { th = 8; tw = 16; }
-  }
-  else if (uses_halo(a)) {
-    if (d->ldo % 4 == 0 && !((uintptr_t)d->out & 15) && ssg_conv_halo_ksplit(a, pick_variant(d)) > 1) return 0;   // split-K launch: no statistics epilogue
-    int bn; ssg_conv_halo_tile(ssg_conv_halo_variant(a, pick_variant(d)), &th, &tw, &bn);
-  }
-  else { th = ssg_conv_dma_variant(a, pick_variant(d)) == 1 ? 16 : 8; tw = 16; }
-  return ((d->GW + tw - 1) / tw) * ((d->GH + th - 1) / th) * d->N;
+  const ConvPlan p = plan_conv(d);
+  if (p.rc != SSG_OK || !p.th) return 0;
+  return ((d->GW + p.tw - 1) / p.tw) * ((d->GH + p.th - 1) / p.th) * d->N;
 }
 
-// bytes of ssg_conv_desc.ws with which the launch for `d` runs split-K (0: this shape / kernel does not split)
-static int64_t splitk_bytes(const ssg_conv_desc* d, int* ksplit) {
-  *ksplit = 1;
-  if (!uses_dma(d)) return 0;
-  const ConvArgs a = to_args(d);
-  if (!uses_halo(a) || d->ldo % 4 || ((uintptr_t)d->out & 15)) return 0;
-  const int k = ssg_conv_halo_ksplit(a, pick_variant(d));
-  if (k <= 1) return 0;
-  *ksplit = k;
-  return (int64_t)k * d->N * d->GH * d->GW * ((d->Cout + 3) & ~3) * (int64_t)sizeof(float);
-}
-
-extern "C" int ssg_conv2d_in_affine_ok(const ssg_conv_desc* d);
-extern "C" int ssg_conv2d_bwd_stats_ok(const ssg_conv_desc* d);
-extern "C" int ssg_conv2d_split_bn(const ssg_conv_desc* d) {
-  if (!d || validate(d) != SSG_OK || ssg_thin4_conv_kind(d) || ssg_thin_conv_kind(d) || ssg_conv1x1_k64_ok(d)) return 0;
-  return split_bn(d);
-}
-
-// 1 when the launch for `d` applies in_scale / in_shift / in_act to its input (ssg_conv_desc.in_scale)
-extern "C" int ssg_conv2d_in_affine_ok(const ssg_conv_desc* d) {
-  if (!d || validate(d) != SSG_OK || !d->w_split || d->parity_merge || d->Cout <= 32) return 0;
-  if (ssg_thin4_conv_kind(d) || ssg_thin_conv_kind(d) || ssg_conv1x1_k64_ok(d)) return 0;
-  const int fmt = split_bn(d);
-  return fmt >= 1000 && ssg_conv_halo_k32_in_affine_ok(to_args(d), fmt) ? 1 : 0;
-}
-
-// 1 when the launch for `d` masks its output and writes the batch-norm backward sums (ssg_conv_desc.bwd_x)
-extern "C" int ssg_conv2d_bwd_stats_ok(const ssg_conv_desc* d) {
-  if (!d || validate(d) != SSG_OK || !d->w_split || d->parity_merge || d->Cout <= 32 || d->res || d->bias || d->act != SSG_ACT_NONE || d->in_scale) return 0;
-  if (ssg_thin4_conv_kind(d) || ssg_thin_conv_kind(d) || ssg_conv1x1_k64_ok(d)) return 0;
-  const int fmt = split_bn(d);
-  return fmt >= 1000 && ssg_conv_halo_k32_bwd_stats_ok(to_args(d), fmt) ? 1 : 0;
-}
-
-extern "C" int64_t ssg_conv2d_workspace_bytes(const ssg_conv_desc* d) {
-  if (!d || validate(d) != SSG_OK || ssg_thin4_conv_kind(d) || ssg_thin_conv_kind(d)) return 0;
-  int k;
-  return splitk_bytes(d, &k);
-}
-
-extern "C" int ssg_conv2d_igemm_f32(const ssg_conv_desc* d, void* stream) {
-  int rc = validate(d);
-  if (rc != SSG_OK) return rc;
-  SSG_REQUIRE(!d->in_scale || (d->in_shift && ssg_conv2d_in_affine_ok(d)), SSG_EINVAL,
-              "conv: in_scale on a descriptor whose kernel has no fused input transform (ssg_conv2d_in_affine_ok == 0)");
-  SSG_REQUIRE(!d->bwd_x || (d->bnpart && d->bwd_scale && d->bwd_shift && d->bwd_mean && ssg_conv2d_bwd_stats_ok(d)), SSG_EINVAL,
-              "conv: bwd_x on a descriptor whose kernel has no backward-statistics epilogue (ssg_conv2d_bwd_stats_ok == 0), or without bnpart");
-  ConvArgs a = to_args(d);
-  hipStream_t st = (hipStream_t)stream;
-  if (d->ws && !d->bnpart) {                 // split-K only with a workspace of the size ssg_conv2d_workspace_bytes reports
-    int k; const int64_t need = splitk_bytes(d, &k);
-    if (need > 0 && d->ws_bytes >= need && !((uintptr_t)d->ws & 15)) { a.ws = d->ws; a.ksplit = k; }
-  }
-  if (d->Cout <= 32 && d->w_split && !d->parity_merge && split_bn(d) >= 1000) {   // narrow k32 tiles
-    SSG_REQUIRE(ssg_aligned16(d->w_split), SSG_EALIGN, "conv: w_split alignment");
-    a.w = (const float*)d->w_split; a.ws = nullptr; a.ksplit = 1;
-    return ssg_conv_igemm_halo_k32_launch(a, split_bn(d), st);
-  }
-  SSG_REQUIRE(!d->bnpart || uses_dma(d), SSG_EINVAL, "conv: bnpart given but this shape has no statistics epilogue (ssg_conv2d_bnpart_rows == 0)");
-  SSG_REQUIRE(!d->parity_merge || (d->w_split && split_bn(d) == 64), SSG_EINVAL,
-              "conv: parity_merge needs a descriptor for which ssg_conv2d_split_bn reports 64 and its w_split pack");
-  if (uses_dma(d)) {
-    if (d->w_split && split_bn(d) > 0) {                 // operands split into bf16 terms on the bf16 matrix pipe
-      SSG_REQUIRE(ssg_aligned16(d->w_split), SSG_EALIGN, "conv: w_split alignment");
-      a.w = (const float*)d->w_split; a.ws = nullptr; a.ksplit = 1;
-      if (d->parity_merge) return ssg_conv_igemm_halo_x3_parity_launch(a, st);
-      if (!uses_halo(a)) return ssg_conv_igemm_dma_x3_launch(a, st);
-      if (split_bn(d) >= 1000) return ssg_conv_igemm_halo_k32_launch(a, split_bn(d), st);
-      return ssg_conv_igemm_halo_x3_launch(a, pick_variant(d), st);
-    }
-    if (uses_halo(a)) return ssg_conv_igemm_halo_launch(a, pick_variant(d), st);
-    return ssg_conv_igemm_dma_launch(a, pick_variant(d), st);
-  }
-  switch (pick_variant(d)) {
-    case 0: return launch<128, 128, 2, 2>(a, st);
-    case 1: return launch<256, 64, 4, 1>(a, st);
-    default: return launch<256, 32, 4, 1>(a, st);
-  }
-}
-
-// Dispatcher: thin VALU kernels for the <= 8-channel cases, MFMA implicit GEMM otherwise.
-// ssg_conv2d_kernel_id reports which kernel a descriptor maps to (for profiling labels):
-//   0..2 = conv_igemm<128,128> / <256,64> / <256,32>, 20/21/22 = conv_igemm_dma<128,128> / <256,64> / <128,64>,
-//   30/31/32 = conv_igemm_halo<128,128> / <256,64> / <128,64>, 33/34 = conv_igemm_halo16<128,128> / <128,64> (8x16-pixel tiles),
-//   12 = thin4 (4x4x1 MFMA) 4-channel input, 13 = thin4 Cout <= 4, 14 = tiny4 (4 -> <= 8 channels, VALU), 15 = thin32
-//   (4-channel input, 3x3, Cout >= 32 on the 32x32x2 MFMA), 16 = conv1x1_k64 (streaming 1x1, 64 input channels),
-//   10 = thin small-Cout (VALU).
-extern "C" int ssg_conv2d_kernel_id(const ssg_conv_desc* d) {
-  if (!d) return SSG_EINVAL;
-  const int k4 = ssg_thin4_conv_kind(d);
-  if (k4) return ssg_thin4_conv_id(d, k4);
-  const int k = ssg_thin_conv_kind(d);
-  if (k) return 9 + k;
-  if (ssg_conv1x1_k64_ok(d)) return 16;
-  if (uses_dma(d)) return uses_halo(to_args(d)) ? 30 + ssg_conv_halo_variant(to_args(d), pick_variant(d)) : 20 + ssg_conv_dma_variant(to_args(d), pick_variant(d));
-  return pick_variant(d);
-}
+extern "C" int ssg_conv2d_igemm_f32(const ssg_conv_desc* d, void* stream) { return launch_plan(d, plan_conv(d, true), stream); }
 
 extern "C" int ssg_conv2d_f32(const ssg_conv_desc* d, void* stream) {
-  int rc = validate(d);
-  if (rc != SSG_OK) return rc;
-  SSG_REQUIRE(!d->in_scale || (d->in_shift && ssg_conv2d_in_affine_ok(d)), SSG_EINVAL,
-              "conv: in_scale on a descriptor whose kernel has no fused input transform (ssg_conv2d_in_affine_ok == 0)");
-  SSG_REQUIRE(!d->bwd_x || (d->bnpart && d->bwd_scale && d->bwd_shift && d->bwd_mean && ssg_conv2d_bwd_stats_ok(d)), SSG_EINVAL,
-              "conv: bwd_x on a descriptor whose kernel has no backward-statistics epilogue (ssg_conv2d_bwd_stats_ok == 0), or without bnpart");
-  SSG_REQUIRE(!d->parity_merge || ssg_conv2d_split_bn(d) == 64, SSG_EINVAL,
+  const ConvPlan p = plan_conv(d);
+  SSG_REQUIRE(p.rc != SSG_OK || !d->parity_merge || p.pack == 64, SSG_EINVAL,
               "conv: parity_merge on a descriptor that has no merged-parity kernel (ssg_conv2d_split_bn != 64)");
-  if (d->parity_merge) return ssg_conv2d_igemm_f32(d, stream);
-  const int k4 = ssg_thin4_conv_kind(d);
-  const int k = k4 ? 0 : ssg_thin_conv_kind(d);
-  SSG_REQUIRE(!d->bnpart || !(k4 || k), SSG_EINVAL, "conv: bnpart given but this shape has no statistics epilogue (ssg_conv2d_bnpart_rows == 0)");
-  if (k4) return ssg_thin4_conv_launch(d, k4, (hipStream_t)stream);
-  if (k) return ssg_thin_conv_launch(d, k, (hipStream_t)stream);
-  if (ssg_conv1x1_k64_ok(d)) return ssg_conv1x1_k64_launch(d, (hipStream_t)stream);
-  return ssg_conv2d_igemm_f32(d, stream);
+  return launch_plan(d, p, stream);
 }

@@ -178,7 +178,9 @@ __global__ __launch_bounds__(32 * ZL) void wgrad_reduce_kernel(const RedArgs a) 
   a.dw[(((size_t)co * a.Cin_real + c) * a.KH + a.ky[t]) * a.KW + a.kx[t]] = v;
 }
 
-struct Plan { int variant, mt, nt, splits, steps_per_split, halo; };
+// kind: 0 = register-staged / LDS-DMA by variant (wgrad_uses_dma), 1 = LDS halo window, 2 = k32, 3 = wgrad4 (variant = its kind)
+enum { WG_MFMA, WG_HALO, WG_K32, WG_4 };
+struct Plan { int variant, mt, nt, splits, steps_per_split, kind; };
 
 // thin weight gradients on the 4x4x1 MFMA (conv_wgrad4.hip); SSG_WGRAD4=0 switches them off (A/B)
 int wgrad4_kind(const ssg_wgrad_desc* d) {
@@ -199,7 +201,13 @@ bool wgrad_uses_halo(const ssg_wgrad_desc* d, int variant) {
 
 Plan make_plan(const ssg_wgrad_desc* d) {
   Plan p;
-  p.halo = 0;
+  p.kind = WG_MFMA;
+  if (const int w4 = wgrad4_kind(d)) {
+    p.kind = WG_4; p.variant = w4;
+    p.mt = p.nt = p.steps_per_split = 0;
+    p.splits = ssg_wgrad4_slices(d, w4, nullptr, nullptr, nullptr);
+    return p;
+  }
   const int Cin = d->C1 + d->C2;
   const int M = d->ntaps * Cin;
   int bn;
@@ -211,13 +219,13 @@ Plan make_plan(const ssg_wgrad_desc* d) {
   long long steps = ((long long)d->N * d->GH * d->GW + BKP - 1) / BKP;
   if (wgrad_uses_halo(d, p.variant)) {
     // M tile = 9 taps x CB channels; a K-step = 16 pixels inside one image row
-    p.halo = 1;
+    p.kind = WG_HALO;
     p.mt = Cin / ssg_wgrad_halo_cb(p.variant);
     steps = (long long)d->N * d->GH * ((d->GW + BKP - 1) / BKP);
   }
   if ((d->flags & 1) && ssg_wgrad_k32_ok(d)) {
     // conv_wgrad_k32.hip: 512-thread workgroups (one per CU) on 9 x 64 x 64 tiles, a K-step = one image row of a 32-pixel column strip
-    p.halo = 2;
+    p.kind = WG_K32;
     p.mt = Cin / 64; p.nt = d->Cout / 64;
     steps = ssg_wgrad_k32_steps(d);
     const long long tiles = (long long)p.mt * p.nt;
@@ -278,8 +286,17 @@ int validate(const ssg_wgrad_desc* d) {
     SSG_REQUIRE(d->dy[t] >= -2 && d->dy[t] <= 5 && d->dx[t] >= -2 && d->dx[t] <= 5, SSG_EINVAL, "wgrad: tap offset");
     SSG_REQUIRE(d->ky[t] >= 0 && d->ky[t] < d->KH && d->kx[t] >= 0 && d->kx[t] < d->KW, SSG_EINVAL, "wgrad: kernel position");
   }
-  SSG_REQUIRE(d->ws_bytes >= ssg_conv2d_wgrad_workspace_bytes(d), SSG_EINVAL, "wgrad: workspace too small");
   return SSG_OK;
+}
+
+int64_t workspace_bytes(const ssg_wgrad_desc* d, const Plan& p) {
+  return (int64_t)p.splits * d->ntaps * (d->C1 + d->C2) * d->Cout * (int64_t)sizeof(float);
+}
+
+// the x operand as a fused batch-norm apply (ssg_wgrad_desc.in_scale): the k32 kernel only, one input pointer
+bool in_affine_ok(const ssg_wgrad_desc* d, const Plan& p) {
+  if (d->C2 != 0 || (d->in_act != SSG_ACT_NONE && d->in_act != SSG_ACT_RELU && d->in_act != SSG_ACT_LRELU)) return false;
+  return p.kind == WG_K32;
 }
 
 __global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restrict__ w, int O, int I, int KH, int KW,
@@ -312,30 +329,22 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restri
 }  // namespace
 
 extern "C" int64_t ssg_conv2d_wgrad_workspace_bytes(const ssg_wgrad_desc* d) {
-  if (!d) return 0;
-  if (wgrad4_kind(d)) {
-    const int nz = ssg_wgrad4_slices(d, wgrad4_kind(d), nullptr, nullptr, nullptr);
-    return (int64_t)nz * d->ntaps * (d->C1 + d->C2) * d->Cout * (int64_t)sizeof(float);
-  }
-  const Plan p = make_plan(d);
-  return (int64_t)p.splits * d->ntaps * (d->C1 + d->C2) * d->Cout * (int64_t)sizeof(float);
+  return d ? workspace_bytes(d, make_plan(d)) : 0;
 }
 
-// the x operand as a fused batch-norm apply (ssg_wgrad_desc.in_scale): the k32 kernel only, one input pointer
 extern "C" int ssg_conv2d_wgrad_in_affine_ok(const ssg_wgrad_desc* d) {
-  if (!d || !d->in1 || !d->dout || wgrad4_kind(d)) return 0;     // asked before the workspace exists: no validate() here
-  if (d->C2 != 0 || (d->in_act != SSG_ACT_NONE && d->in_act != SSG_ACT_RELU && d->in_act != SSG_ACT_LRELU)) return 0;
-  return make_plan(d).halo == 2 ? 1 : 0;
+  if (!d || !d->in1 || !d->dout) return 0;     // asked before the workspace exists: no validate() here
+  return in_affine_ok(d, make_plan(d)) ? 1 : 0;
 }
 
 extern "C" int ssg_conv2d_wgrad_f32(const ssg_wgrad_desc* d, void* stream) {
   int rc = validate(d);
   if (rc != SSG_OK) return rc;
-  SSG_REQUIRE(!d->in_scale || (d->in_shift && ssg_conv2d_wgrad_in_affine_ok(d)), SSG_EINVAL,
+  const Plan p = make_plan(d);
+  SSG_REQUIRE(d->ws_bytes >= workspace_bytes(d, p), SSG_EINVAL, "wgrad: workspace too small");
+  SSG_REQUIRE(!d->in_scale || (d->in_shift && in_affine_ok(d, p)), SSG_EINVAL,
               "wgrad: in_scale on a descriptor whose kernel has no fused input transform (ssg_conv2d_wgrad_in_affine_ok == 0)");
-  Plan p = make_plan(d);
   hipStream_t st = (hipStream_t)stream;
-  const int w4 = wgrad4_kind(d);
   WgArgs a;
   a.in1 = d->in1; a.in2 = d->C2 ? d->in2 : d->in1; a.dout = d->dout; a.ws = d->ws;
   a.C1 = d->C1; a.C2 = d->C2; a.ld1 = d->ld1; a.ld2 = d->C2 ? d->ld2 : d->ld1;
@@ -348,16 +357,15 @@ extern "C" int ssg_conv2d_wgrad_f32(const ssg_wgrad_desc* d, void* stream) {
   a.M = d->ntaps * (d->C1 + d->C2);
   a.Ptot = (long long)d->N * d->GH * d->GW;
   a.steps_per_split = p.steps_per_split;
-  if (w4) {
-    p.splits = ssg_wgrad4_slices(d, w4, nullptr, nullptr, nullptr);
-    rc = ssg_wgrad4_launch(d, w4, st);
+  if (p.kind == WG_4) {
+    rc = ssg_wgrad4_launch(d, p.variant, st);
     if (rc != SSG_OK) return rc;
   } else {
     dim3 grid((unsigned)p.mt, (unsigned)p.nt, (unsigned)p.splits);
-    if (p.halo == 2) {
+    if (p.kind == WG_K32) {
       rc = ssg_wgrad_k32_launch(a, grid, st);
       if (rc != SSG_OK) return rc;
-    } else if (p.halo) {
+    } else if (p.kind == WG_HALO) {
       rc = ssg_wgrad_halo_launch(a, p.variant, grid, st, (d->flags & 1) != 0);
       if (rc != SSG_OK) return rc;
     } else if (wgrad_uses_dma(p.variant)) {
@@ -419,9 +427,9 @@ extern "C" int ssg_pack_weights_scaled_f32(const float* w_oihw, int O, int I, in
 // which kernel a wgrad descriptor maps to: 0..2 = wgrad<128,128>/<128,64>/<128,32>, 20/21 = wgrad_dma<128,128>/<128,64>, 30/31 = wgrad_halo<32,128>/<64,64>, 40/41 / 50/51 = the split-operand (x3) forms of 30/31 / 20/21, 60 = wgrad_k32 (conv_wgrad_k32.hip), 15/16 = wgrad4 (4x4x1 MFMA)
 extern "C" int ssg_conv2d_wgrad_kernel_id(const ssg_wgrad_desc* d) {
   if (!d) return SSG_EINVAL;
-  if (wgrad4_kind(d)) return 10 + wgrad4_kind(d);
-  if (make_plan(d).halo == 2) return 60;
-  if (make_plan(d).halo) return ((d->flags & 1) ? 40 : 30) + make_plan(d).variant;
-  const int v = make_plan(d).variant;
-  return v + (wgrad_uses_dma(v) ? ((d->flags & 1) ? 50 : 20) : 0);
+  const Plan p = make_plan(d);
+  if (p.kind == WG_4) return 10 + p.variant;
+  if (p.kind == WG_K32) return 60;
+  if (p.kind == WG_HALO) return ((d->flags & 1) ? 40 : 30) + p.variant;
+  return p.variant + (wgrad_uses_dma(p.variant) ? ((d->flags & 1) ? 50 : 20) : 0);
 }

@@ -235,6 +235,10 @@ _CONV_LABELS = {0: 'conv_igemm_kernel<128,128>', 1: 'conv_igemm_kernel<256,64>',
                 20: 'conv_igemm_dma_kernel<128,128>', 21: 'conv_igemm_dma_kernel<256,64>', 22: 'conv_igemm_dma_kernel<128,64>',
                 30: 'conv_igemm_halo_kernel<128,128>', 31: 'conv_igemm_halo_kernel<256,64>', 32: 'conv_igemm_halo_kernel<128,64>',
                 33: 'conv_igemm_halo16_kernel<128,128>', 34: 'conv_igemm_halo16_kernel<128,64>',
+                40: 'conv_igemm_halo_x3_kernel<128,128>', 41: 'conv_igemm_halo_x3_kernel<128,64>',
+                42: 'conv_igemm_halo_x3_kernel<128,64,4,1,true>', 50: 'conv_igemm_dma_x3_kernel<64>', 51: 'conv_igemm_dma_x3_kernel<128>',
+                60: 'conv_halo_k32_kernel<8,128>', 61: 'conv_halo_k32_kernel<4,64>', 62: 'conv_halo_k32_kernel<16,64>',
+                63: 'conv_halo_k32_kernel<8,16>', 64: 'conv_halo_k32_kernel<8,32>',
                 10: 'thin_small_cout_kernel',
                 12: 'thin4_cin_kernel', 13: 'thin4_cout_kernel', 14: 'tiny4_kernel', 15: 'thin32_cin_kernel', 16: 'conv1x1_k64_kernel'}
 _WGRAD_LABELS = {0: 'wgrad_kernel<128,128>', 1: 'wgrad_kernel<128,64>', 2: 'wgrad_kernel<128,32>',
@@ -262,17 +266,19 @@ class _Timed(object):
             PROFILE.append((self.label, self.flops, self.e0, self.e1, self.tag))
 
 
-_DECLINED = object()      # _conv_launch: the library has no kernel with the fused input transform for this launch (nothing was launched)
+class _Declined(Exception):
+    """_conv_launch: the library has no kernel for this parity-merged / in_affine / bwd_stats launch (nothing was allocated or launched)."""
 
 
 def _conv_launch(x1, x2, wpk, kp, kmode, row0, cout, bias, res, act, slope, taps, n, h, w, gh, gw, oh, ow,
                  in_s, out_s, out_oy, out_ox, out, want_bn=False, tag=None, parity_merge=False, in_affine=None, bwd_stats=None):
     """Returns None, or -- with want_bn and a kernel that has the statistics epilogue -- the fp64 tensor [rows, 2, cout] of
     per-tile (sum, sum of squares) of the conv output (ssg_conv_desc.bnpart).  parity_merge: the nine taps are the four parity
-    classes of a 3x3 stride-2 input gradient (ssg_conv_desc.parity_merge); returns False, with nothing launched, when the library
-    has no merged kernel for this shape.  in_affine = (scale[C1], shift[C1], act, slope): the launch convolves act(x1 * scale +
-    shift) (ssg_conv_desc.in_scale: a batch-norm apply that is never materialised); returns _DECLINED, with nothing launched, when
-    the kernel this shape maps to has no such transform."""
+    classes of a 3x3 stride-2 input gradient (ssg_conv_desc.parity_merge).  in_affine = (scale[C1], shift[C1], act, slope): the
+    launch convolves act(x1 * scale + shift) (ssg_conv_desc.in_scale: a batch-norm apply that is never materialised).
+    bwd_stats = (x, stats rows [mean, invstd, scale, shift], act, slope): the launch produces d(act(bn(x))), masks it and writes the
+    batch-norm backward sums as per-tile rows (ssg_conv_desc.bwd_x).  Raises _Declined, with nothing allocated or launched, where
+    the library has no kernel for a parity_merge / in_affine / bwd_stats launch."""
     d = ConvDesc()
     d.in1 = x1.data_ptr(); d.C1 = pad4(x1.shape[1]); d.ld1 = _ld(x1)
     if x2 is not None:
@@ -299,36 +305,30 @@ def _conv_launch(x1, x2, wpk, kp, kmode, row0, cout, bias, res, act, slope, taps
     d.parity_merge = 1 if parity_merge else 0
     d.in_scale = None; d.in_shift = None; d.in_act = ACT_NONE; d.in_slope = 0.0
     d.bwd_x = None; d.bwd_ldx = 0; d.bwd_scale = None; d.bwd_shift = None; d.bwd_mean = None; d.bwd_act = ACT_NONE; d.bwd_slope = 0.0
-    split = None
-    if parity_merge and not (MFMA_SPLIT and kmode == 0 and call('ssg_conv2d_split_bn', C.byref(d)) == 64):
-        return False
-    if MFMA_SPLIT and kmode == 0:      # decided first: the split-operand kernel has its own tile geometry (bnpart rows)
-        bn = call('ssg_conv2d_split_bn', C.byref(d))
-        if bn:
-            split = _split_pack(wpk, row0, cout, kp, 1064 if bn == 2064 else bn)      # 2064: the 16-row tile reads the 64-column k32 pack
-            d.w_split = split.data_ptr()
+    pack = call('ssg_conv2d_split_bn', C.byref(d)) if MFMA_SPLIT and kmode == 0 else 0
+    if parity_merge and pack != 64:
+        raise _Declined()
+    d.w_split = 1 if pack else None         # placeholder until the pack exists: the queries below depend on the kernel it selects
     if in_affine is not None:
         d.in_scale = in_affine[0].data_ptr(); d.in_shift = in_affine[1].data_ptr(); d.in_act = int(in_affine[2]); d.in_slope = float(in_affine[3])
-        if split is None or not call('ssg_conv2d_in_affine_ok', C.byref(d)):
-            return _DECLINED
-        bn = call('ssg_conv2d_split_bn', C.byref(d))      # with the transform a 16-row launch becomes a 4-row one (same pack)
+        if not call('ssg_conv2d_in_affine_ok', C.byref(d)):
+            raise _Declined()
     if bwd_stats is not None:
-        # (x, stats rows [mean, invstd, scale, shift], act, slope): the launch produces d(act(bn(x))), masks it and writes the batch-norm
-        # backward sums as per-tile rows (ssg_conv_desc.bwd_x); _DECLINED, with nothing launched, where the kernel has no such epilogue
         bx, bst, bact, bslope = bwd_stats
         d.bwd_x = bx.data_ptr(); d.bwd_ldx = _ld(bx); d.bwd_scale = bst[2].data_ptr(); d.bwd_shift = bst[3].data_ptr()
         d.bwd_mean = bst[0].data_ptr(); d.bwd_act = int(bact); d.bwd_slope = float(bslope)
-        if split is None or not call('ssg_conv2d_bwd_stats_ok', C.byref(d)):
-            return _DECLINED
+        if not call('ssg_conv2d_bwd_stats_ok', C.byref(d)):
+            raise _Declined()
         want_bn = True
+    rows = call('ssg_conv2d_bnpart_rows', C.byref(d)) if want_bn and BN_EPILOGUE else 0
+    if bwd_stats is not None and rows == 0:
+        raise _Declined()
+    split = _split_pack(wpk, row0, cout, kp, pack) if pack else None
+    d.w_split = split.data_ptr() if split is not None else None
     part = None
-    if want_bn and BN_EPILOGUE:
-        rows = call('ssg_conv2d_bnpart_rows', C.byref(d))
-        if rows > 0:
-            part = torch.empty((rows, 2, cout), dtype=torch.float64, device=out.device)
-            d.bnpart = part.data_ptr()
-    if bwd_stats is not None and part is None:
-        return _DECLINED
+    if rows > 0:
+        part = torch.empty((rows, 2, cout), dtype=torch.float64, device=out.device)
+        d.bnpart = part.data_ptr()
     ws = None
     if part is None and split is None:  # split-K (small pixel grids with a long reduction): the kernel needs a workspace
         need = call('ssg_conv2d_workspace_bytes', C.byref(d))
@@ -339,16 +339,6 @@ def _conv_launch(x1, x2, wpk, kp, kmode, row0, cout, bias, res, act, slope, taps
     label = None
     if PROFILE is not None:
         label = _CONV_LABELS.get(call('ssg_conv2d_kernel_id', C.byref(d)), '?') + ('+splitk' if ws is not None else '')
-        if parity_merge:
-            label = 'conv_igemm_halo_x3_kernel<128,64,4,1,true>'
-        elif split is not None and bn >= 1000:
-            label = {1128: 'conv_halo_k32_kernel<8,128>', 1064: 'conv_halo_k32_kernel<4,64>', 2064: 'conv_halo_k32_kernel<16,64>',
-                     1016: 'conv_halo_k32_kernel<8,16>', 1032: 'conv_halo_k32_kernel<8,32>'}[bn]
-        elif split is not None:
-            if 'halo' in label:
-                label = label.replace('conv_igemm_halo_kernel', 'conv_igemm_halo_x3_kernel').replace('<256,64>', '<128,64>')
-            else:
-                label = 'conv_igemm_dma_x3_kernel<%d>' % bn
         if PROFILE_SHAPES:
             label += ' n%d %dx%d cin%d cout%d taps%d s%d/%d' % (n, gh, gw, cred, cout, len(taps), in_s, out_s)
     with _Timed(label, 2.0 * n * gh * gw * cout * cred * len(taps), tag):
@@ -418,10 +408,11 @@ def _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=None, out=
     oh, ow = _out_hw(h, w, kh, kw, stride, pad)
     if out is None:
         out = new_nhwc(n, o, oh, ow, x1.device)
-    part = _conv_launch(x1, x2, wpk, kp, kmode, 0, o, bias, res, act, slope, taps, n, h, w, oh, ow, oh, ow, stride, 1, 0, 0, out,
-                        want_bn=want_bn and res is None and act == ACT_NONE,
-                        tag=_ROLE[0] if (kh == 3 and kw == 3 and _ROLE[0] is not None) else None, in_affine=in_affine)
-    if part is _DECLINED:
+    try:
+        part = _conv_launch(x1, x2, wpk, kp, kmode, 0, o, bias, res, act, slope, taps, n, h, w, oh, ow, oh, ow, stride, 1, 0, 0, out,
+                            want_bn=want_bn and res is None and act == ACT_NONE,
+                            tag=_ROLE[0] if (kh == 3 and kw == 3 and _ROLE[0] is not None) else None, in_affine=in_affine)
+    except _Declined:
         return None
     return (out, part) if want_bn else out
 
@@ -440,11 +431,12 @@ def _conv_dgrad_impl(dy, weight, stride, pad, h, w, c_lo, c_hi, res=None, wscale
     if stride == 1:
         taps = [(ky, kx, pt - ky, pl - kx) for ky in range(kh) for kx in range(kw)]
         wpk, kp, kmode = _pack(weight, 1, taps, cred_pad, cred_pad, sigma=wscale)
-        part = _conv_launch(dy, None, wpk, kp, kmode, c_lo, c_hi - c_lo, None, res, ACT_NONE, 0.0, taps, n, oh, ow, h, w, h, w, 1, 1, 0, 0, dx,
-                            bwd_stats=bwd_stats)
-        if bwd_stats is not None:
-            return None if part is _DECLINED else (dx, part)
-        return dx
+        try:
+            part = _conv_launch(dy, None, wpk, kp, kmode, c_lo, c_hi - c_lo, None, res, ACT_NONE, 0.0, taps, n, oh, ow, h, w, h, w, 1, 1, 0, 0,
+                                dx, bwd_stats=bwd_stats)
+        except _Declined:
+            return None
+        return dx if bwd_stats is None else (dx, part)
     if bwd_stats is not None:
         return None
     if res is not None:
@@ -465,9 +457,12 @@ def _conv_dgrad_impl(dy, weight, stride, pad, h, w, c_lo, c_hi, res=None, wscale
         # (conv_igemm_halo_x3_kernel<..., PARITY>); falls through to the per-class launches where the library declines
         merged = [t for _, _, taps in classes for t in taps]
         wpk, kp, kmode = _pack(weight, 1, merged, cred_pad, cred_pad, sigma=wscale)
-        if _conv_launch(dy, None, wpk, kp, kmode, c_lo, c_hi - c_lo, None, None, ACT_NONE, 0.0, merged, n, oh, ow,
-                        (h + 1) // 2, (w + 1) // 2, h, w, 1, s, 0, 0, dx, parity_merge=True) is not False:
+        try:
+            _conv_launch(dy, None, wpk, kp, kmode, c_lo, c_hi - c_lo, None, None, ACT_NONE, 0.0, merged, n, oh, ow,
+                         (h + 1) // 2, (w + 1) // 2, h, w, 1, s, 0, 0, dx, parity_merge=True)
             return dx
+        except _Declined:
+            pass
     if any(len(t) == 0 for _, _, t in classes):
         dx.zero_()
     for py, px, taps in classes:
