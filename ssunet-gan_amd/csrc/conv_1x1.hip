@@ -11,7 +11,6 @@
 // rows past the end get offset 0xffffffff (dropped by the range check) instead of a branch.
 #include "common.h"
 #include "conv_thin.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -120,8 +119,7 @@ __global__ __launch_bounds__(256) void conv1x1_k64_kernel(const C11Args a) {
 
 // 1 = this descriptor is a plain 1x1, 64-input-channel conv over a whole contiguous pixel range that the streaming kernel takes
 int ssg_conv1x1_k64_ok(const ssg_conv_desc* d) {
-  static const int on = [] { const char* e = getenv("SSG_CONV1X1_STREAM"); return e ? atoi(e) : 1; }();     // 0: LDS-DMA kernel (A/B)
-  if (!on || d->ntaps != 1 || d->dy[0] || d->dx[0] || d->C1 != 64 || d->C2 != 0 || d->kmode != 0 || d->Kp != 64 || d->bnpart) return 0;
+  if (d->ntaps != 1 || d->dy[0] || d->dx[0] || d->C1 != 64 || d->C2 != 0 || d->kmode != 0 || d->Kp != 64 || d->bnpart) return 0;
   if (d->in_sy != 1 || d->in_sx != 1 || d->out_sy != 1 || d->out_sx != 1 || d->out_oy || d->out_ox) return 0;
   if (d->GH != d->H || d->GW != d->W || d->OH != d->H || d->OW != d->W) return 0;
   const long long P = (long long)d->N * d->H * d->W;

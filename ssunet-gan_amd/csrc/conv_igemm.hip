@@ -20,11 +20,6 @@
 #include "common.h"
 #include "conv_thin.h"
 #include "conv_args.h"
-#include <stdlib.h>
-
-#ifndef SSG_EXPERIMENT
-#define SSG_EXPERIMENT 0
-#endif
 
 namespace {
 
@@ -142,9 +137,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a) {
   for (int s = 0; s < a.nsteps; ++s) {
     const int buf = s & 1;
     const bool more = (s + 1) < a.nsteps;
-#if SSG_EXPERIMENT != 1
     if (more) load_step(s + 1);
-#endif
     const float* Ab = As + buf * BM * LDS_ROW + (wm * WTM + l31) * LDS_ROW + 4 * half;
     const float* Bb = Bs + buf * BN * LDS_ROW + (wn * WTN + l31) * LDS_ROW + 4 * half;
 #pragma unroll
@@ -162,12 +155,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a) {
           for (int j = 0; j < NI; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][e], fb[j][e], acc[i][j], 0, 0, 0);
     }
-#if SSG_EXPERIMENT != 1 && SSG_EXPERIMENT != 2
     if (more) store_step(buf ^ 1);
-#elif SSG_EXPERIMENT == 2
-    for (int j = 0; j < A_LD; ++j) asm volatile("" :: "v"(ra[j]));
-    for (int j = 0; j < B_LD; ++j) asm volatile("" :: "v"(rb[j]));
-#endif
     __syncthreads();
   }
 
@@ -219,28 +207,23 @@ int pick_variant(const ssg_conv_desc* d) {
   return 2;                         // 256 x 32
 }
 
-// LDS-DMA pipeline (conv_igemm_dma.hip) for the dense layers; SSG_IGEMM_DMA=0 falls back to the
-// register-staged kernel (A/B switch for measurements).
+// LDS-DMA pipeline (conv_igemm_dma.hip) for the dense layers; kmode 1 and the narrow outputs below stay on the
+// register-staged kernel.
 ConvArgs to_args(const ssg_conv_desc* d);
 bool uses_halo(const ConvArgs& a);
 
 bool uses_dma(const ssg_conv_desc* d) {
-  static const int use_dma = [] { const char* e = getenv("SSG_IGEMM_DMA"); return e ? atoi(e) : 1; }();
-  if (!use_dma || d->kmode != 0) return false;
+  if (d->kmode != 0) return false;
   if (d->Cout > 32) return true;
   // Cout 17..32 on a small pixel grid with a long reduction (the input gradient of SPADE's gamma|beta conv at the 32x32
   // level: 1024 -> 32 on 16 384 pixels = 64 tiles of the 256x32 register kernel): the 64-wide halo tile multiplies half
   // its columns by zero weights but splits K over the idle CUs (15 -> > 60 TFLOP/s)
-  static const int narrow = [] { const char* e = getenv("SSG_HALO_NARROW"); return e ? atoi(e) : 1; }();
-  return narrow && d->Cout > 16 && d->ntaps == 9 && d->in_sy == 1 && d->in_sx == 1 && d->C1 + d->C2 >= 256 &&
+  return d->Cout > 16 && d->ntaps == 9 && d->in_sy == 1 && d->in_sx == 1 && d->C1 + d->C2 >= 256 &&
          (long long)d->N * d->GH * d->GW <= 32768 && uses_halo(to_args(d));
 }
 
-// LDS-resident halo tile (conv_igemm_halo.hip) for the 3x3 window; SSG_IGEMM_HALO=0 switches it off (A/B)
-bool uses_halo(const ConvArgs& a) {
-  static const int on = [] { const char* e = getenv("SSG_IGEMM_HALO"); return e ? atoi(e) : 1; }();
-  return on && ssg_conv_halo_ok(a);
-}
+// LDS-resident halo tile (conv_igemm_halo.hip) for the 3x3 window
+bool uses_halo(const ConvArgs& a) { return ssg_conv_halo_ok(a); }
 
 int validate(const ssg_conv_desc* d) {
   SSG_REQUIRE(d != nullptr, SSG_EINVAL, "conv: null desc");

@@ -19,19 +19,12 @@
 #include "lds_dma.h"
 #include "conv_args.h"
 
-#ifndef SSG_EXPERIMENT
-#define SSG_EXPERIMENT 0
-#endif
-
 namespace {
 
 __device__ __attribute__((aligned(64))) float ssg_zero_page[64];
 
 
-#ifndef SSG_DMA_STAGES
-#define SSG_DMA_STAGES 3
-#endif
-constexpr int NSTAGE = SSG_DMA_STAGES;      // LDS stages; NSTAGE-1 K-steps are in flight across each barrier
+constexpr int NSTAGE = 3;     // LDS stages; NSTAGE-1 K-steps are in flight across each barrier
 constexpr int AHEAD = NSTAGE - 1;
 
 template <int BM, int BN, int WAVES_M, int WAVES_N>
@@ -97,7 +90,6 @@ __global__ __launch_bounds__(256) void conv_igemm_dma_kernel(const ConvArgs a) {
     const int c0 = chunk * 16;
     const float* src; int ld, cc;
     if (c0 < a.C1) { src = a.in1; ld = a.ld1; cc = c0; } else { src = a.in2; ld = a.ld2; cc = c0 - a.C1; }
-#if SSG_EXPERIMENT != 3
 #pragma unroll
     for (int j = 0; j < A_PC; ++j) {
       const int iy = a_iy0[j] + dy, ix = a_ix0[j] + dx;
@@ -105,14 +97,11 @@ __global__ __launch_bounds__(256) void conv_igemm_dma_kernel(const ConvArgs a) {
       const float* p = ok ? src + ((size_t)(n * a.H + iy) * a.W + ix) * ld + cc + a_q[j] : zero;
       dma16(p, st + (wave * A_PC + j) * 256);
     }
-#endif
-#if SSG_EXPERIMENT != 4
 #pragma unroll
     for (int j = 0; j < B_PC; ++j) {
       const float* p = b_src[j] ? b_src[j] + (size_t)s * 16 : zero;
       dma16(p, st + BM * 16 + (wave * B_PC + j) * 256);
     }
-#endif
   };
 
   f32x16 acc[MI][NI];
@@ -136,10 +125,6 @@ __global__ __launch_bounds__(256) void conv_igemm_dma_kernel(const ConvArgs a) {
   for (int s = 0; s < nsteps; ++s) {
     // steps s+1 .. s+AHEAD-1 may stay in flight; near the tail fewer are outstanding
     const int rem = nsteps - 1 - s;
-#if SSG_EXPERIMENT == 3 || SSG_EXPERIMENT == 4
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (false)
-#endif
     if (rem >= AHEAD - 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - 1) * (A_PC + B_PC)) : "memory");
     else if (AHEAD >= 3 && rem == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_PC + B_PC) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -213,8 +198,7 @@ int launch(const ConvArgs& a0, hipStream_t st) {
   constexpr int TH = BM / 16;
   a.tiles_x = (a.GW + 15) / 16;
   a.tiles_y = (a.GH + TH - 1) / TH;
-  static const int swz = [] { const char* e = getenv("SSG_XCD_SWIZZLE"); return e ? atoi(e) : 1; }();
-  a.xcd_swizzle = swz;
+  a.xcd_swizzle = ssg_xcd_swizzle();
   a.ntiles_n = (a.Cout + BN - 1) / BN;
   dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N * a.ntiles_n));
   constexpr int lds_bytes = NSTAGE * (BM + BN) * 16 * (int)sizeof(float);
@@ -236,8 +220,7 @@ int launch(const ConvArgs& a0, hipStream_t st) {
 // stride-2 input gradient): a tile is mostly prologue and epilogue, and four small workgroups per CU overlap those
 // better than two or three large ones (measured: <= 16 steps -1.4 ms/step, 36 or 72 no better).
 int ssg_conv_dma_variant(const ConvArgs& a, int variant) {
-  static const int small_k = [] { const char* e = getenv("SSG_DMA_SMALLK"); return e ? atoi(e) : 16; }();
-  if (small_k && a.nsteps <= small_k) return 2;
+  if (a.nsteps <= 16) return 2;
   return variant == 0 ? 0 : 1;
 }
 

@@ -135,16 +135,15 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma_x3_kernel(const ConvArg
 #define SSG_X3_TERM(A, B)                                                                           \
   _Pragma("unroll") for (int j = 0; j < NI; ++j)                                                   \
       acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B[j], acc[j], 0, 0, 0);
-#ifndef SSG_X3_DYNPRIO
-#define SSG_X3_DYNPRIO 1                                   // 1: wave priority falls through the step's six terms (as the k32 kernels).  Same-box A/B: +3-4 % here (stride-2 / 1x1 forward); the same in wgrad_dma_x3 lost 2-3 % and in the merged-parity halo kernel changed nothing: not there
-#endif
-    if (SSG_X3_DYNPRIO) __builtin_amdgcn_s_setprio(3);
+    // wave priority falls through the step's six terms (as the k32 kernels).  Same-box A/B against a flat priority:
+    // +3-4 % here (stride-2 / 1x1 forward); the same in wgrad_dma_x3 lost 2-3 % and in the merged-parity halo kernel changed nothing: not there
+    __builtin_amdgcn_s_setprio(3);
     SSG_X3_TERM(a3, b1) SSG_X3_TERM(a2, b2)
-    if (SSG_X3_DYNPRIO) __builtin_amdgcn_s_setprio(2);
+    __builtin_amdgcn_s_setprio(2);
     SSG_X3_TERM(a1, b3)
-    if (SSG_X3_DYNPRIO) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
     SSG_X3_TERM(a2, b1) SSG_X3_TERM(a1, b2)
-    if (SSG_X3_DYNPRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     SSG_X3_TERM(a1, b1)
 #undef SSG_X3_TERM
   }
@@ -203,8 +202,7 @@ int launch(const ConvArgs& a0, hipStream_t st) {
   ConvArgs a = a0;
   a.tiles_x = (a.GW + 15) / 16;
   a.tiles_y = (a.GH + 7) / 8;
-  static const int swz = [] { const char* e = getenv("SSG_XCD_SWIZZLE"); return e ? atoi(e) : 1; }();
-  a.xcd_swizzle = swz;
+  a.xcd_swizzle = ssg_xcd_swizzle();
   a.ntiles_n = (a.Cout + BN - 1) / BN;
   dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N * a.ntiles_n));
   constexpr int lds_bytes = NSTAGE * (128 * 64 + BN * XROW) + 1024;

@@ -27,12 +27,6 @@ namespace {
 
 __device__ __attribute__((aligned(64))) float ssg_zero_page_h[64];
 
-#ifndef SSG_HALO_EXP
-#define SSG_HALO_EXP 0     // ablation builds (tools/micro_halo_exp.py), never shipped: 1 = one barrier per chunk instead of per
-#endif                     // step, 2 = no weight DMA, 3 = both, 4 = s_setprio around the MFMA block, 5/6/7 = A / B / both DMA sources = zero page, 8 = contiguous B pieces
-
-
-
 #ifdef SSG_CLOCK_PROBE
 // diagnostic build only (tools/clock_probe.py): per workgroup (shader cycles, 100-MHz ticks) spent in the main loop
 __device__ unsigned long long* ssg_probe_buf = nullptr;
@@ -115,9 +109,6 @@ __device__ __forceinline__ void halo_body(const ConvArgs& a) {
     const float* src; int ld, cc;
     if (c0 < a.C1) { src = a.in1; ld = a.ld1; cc = c0; } else { src = a.in2; ld = a.ld2; cc = c0 - a.C1; }
     const float* p = (chunk < nchunks && a_pix[k] >= 0) ? src + (size_t)a_pix[k] * ld + cc + a_q[k] : zero;
-#if SSG_HALO_EXP == 5 || SSG_HALO_EXP == 7
-    p = zero + (lane & 3) * 4;                           // every A piece from the (cache-resident) zero page
-#endif
     dma16(p, dst);
   };
   auto issue_b = [&](int s) {
@@ -125,12 +116,6 @@ __device__ __forceinline__ void halo_body(const ConvArgs& a) {
 #pragma unroll
     for (int j = 0; j < B_PC; ++j) {
       const float* p = (b_src[j] && s < nsteps) ? b_src[j] + (size_t)s * 16 : zero;
-#if SSG_HALO_EXP == 6 || SSG_HALO_EXP == 7
-      p = zero + (lane & 3) * 4;                         // every B piece from the zero page
-#endif
-#if SSG_HALO_EXP == 8                                    // B pieces from 1-KiB contiguous runs (what a step-major pack would give)
-      if (s < nsteps) p = a.w + ((size_t)(n0 / BN) * nsteps + s) * BSTG + (wave * B_PC + j) * 256 + lane * 4;
-#endif
       dma16(p, st + (wave * B_PC + j) * 256);
     }
   };
@@ -179,19 +164,11 @@ __device__ __forceinline__ void halo_body(const ConvArgs& a) {
       if (tp < APW - 1) wait_vmcnt<B_PC + 1>();
       else if (tp == APW - 1) { if (has_last) wait_vmcnt<B_PC + 1>(); else wait_vmcnt<B_PC>(); }
       else wait_vmcnt<B_PC>();
-#if SSG_HALO_EXP == 1 || SSG_HALO_EXP == 3
-      if (t == 0) __builtin_amdgcn_s_barrier();
-#else
       wait_lds_reads();                                  // lds_dma.h: the barrier hands stage (s + 2) % 3 to another wave's DMA
       __builtin_amdgcn_s_barrier();
-#endif
       asm volatile("" ::: "memory");
       if (t < APW) issue_a(chunk + 1, t);
-#if SSG_HALO_EXP == 2 || SSG_HALO_EXP == 3
-      if (t >= APW) dma16(zero, ldsB + (s % 3) * BSTG + wave * 256);     // keeps the vmcnt arithmetic alive with one piece
-#else
       issue_b(s + 2);
-#endif
 
       const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);
       const int toff = ((tb & 7) - 2) * HW + ((tb >> 3) - 2);          // dy*HW + dx
@@ -208,9 +185,6 @@ __device__ __forceinline__ void halo_body(const ConvArgs& a) {
         const int bq = h == 0 ? bq0 : bq1;
 #pragma unroll
         for (int j = 0; j < NI; ++j) fb[j] = *(const f32x4*)(Bb + j * 32 * 16 + bq);
-#if SSG_HALO_EXP == 4
-        __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
         for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -218,9 +192,6 @@ __device__ __forceinline__ void halo_body(const ConvArgs& a) {
 #pragma unroll
             for (int j = 0; j < NI; ++j)
               acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][e], fb[j][e], acc[i][j], 0, 0, 0);
-#if SSG_HALO_EXP == 4
-        __builtin_amdgcn_s_setprio(0);
-#endif
       }
     }
   }
@@ -285,8 +256,7 @@ int launch(const ConvArgs& a0, hipStream_t st) {
   constexpr int AP = ((TH + 2) * (TWL == 5 ? TW + 2 : 32) + 15) / 16;
   a.tiles_x = (a.GW + TW - 1) / TW;
   a.tiles_y = (a.GH + TH - 1) / TH;
-  static const int swz = [] { const char* e = getenv("SSG_XCD_SWIZZLE"); return e ? atoi(e) : 1; }();
-  a.xcd_swizzle = swz;
+  a.xcd_swizzle = ssg_xcd_swizzle();
   a.ntiles_n = (a.Cout + BN - 1) / BN;
   if (a.ksplit < 1) a.ksplit = 1;
   dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N * a.ntiles_n * a.ksplit));
@@ -351,8 +321,7 @@ void ssg_conv_halo_tile(int v, int* th, int* tw, int* bn) {
 // (measured at 16x512^2: Cin=64 108 -> 122 TFLOP/s, Cin=128 123 -> 128, Cin=192 132 -> 130)
 // 3 / 4 = <128,128> / <128,64> with 8 x 16-pixel tiles, for images at most 16 pixels wide.
 int ssg_conv_halo_variant(const ConvArgs& a, int variant) {
-  static const int w16 = [] { const char* e = getenv("SSG_HALO_W16"); return e ? atoi(e) : 1; }();
-  if (w16 && a.GW <= 16) return (variant == 0) ? 3 : 4;
+  if (a.GW <= 16) return (variant == 0) ? 3 : 4;
   // Cout > 64 with Cin = 64 on the largest grids also prefers two <128,64> column tiles (110 -> 120 at 16x512^2)
   if (variant == 0) {            // fewer than 3 workgroups per CU with 128x128 tiles: halve the tile (32x32 level)
     const long long wgs = (long long)a.N * ((a.GH + 3) / 4) * ((a.GW + 31) / 32) * ((a.Cout + 127) / 128);
@@ -365,10 +334,9 @@ int ssg_conv_halo_variant(const ConvArgs& a, int variant) {
 }
 
 // Split-K factor for a launch: as many slabs as bring the grid to ~3 workgroups per CU, each slab keeping at least 4
-// chunks (36 K-steps); 1 when the grid already fills the chip or no workspace was given.  SSG_HALO_SPLITK=0 switches it off.
+// chunks (36 K-steps); 1 when the grid already fills the chip or no workspace was given.
 int ssg_conv_halo_ksplit(const ConvArgs& a, int variant) {
-  static const int on = [] { const char* e = getenv("SSG_HALO_SPLITK"); return e ? atoi(e) : 1; }();
-  if (!on || a.bnpart) return 1;
+  if (a.bnpart) return 1;
   int th, tw, bn;
   const int hv = ssg_conv_halo_variant(a, variant);
   if (hv == 0 || hv == 1) return 1;                         // <128,128> / <256,64> on 32-wide tiles are only picked for grids that fill the chip

@@ -25,7 +25,6 @@
 #include "conv_args.h"
 #include "mfma_split.h"
 #include "conv_slow.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -41,8 +40,19 @@ __device__ unsigned long long* ssg_probe_buf_k32 = nullptr;
 #define SSG_STAMP(i) do { if (ssg_probe_buf_k32 && tid == 0) { ssg_probe_buf_k32[SSG_PROBE_SLOTS * blockIdx.x + (i)] = __builtin_amdgcn_s_memtime(); \
                                                             if ((i) == 0 || (i) == 3) ssg_probe_buf_k32[SSG_PROBE_SLOTS * blockIdx.x + 4 + ((i) == 3)] = __builtin_amdgcn_s_memrealtime(); } } while (0)
 #define SSG_PROBE_NOW(v) unsigned long long v = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(v) :: "memory")
-#else
+// the per-wave sums of slots 8 ..: declared before the main loop, one SSG_PROBE_STEP per K-step from three SSG_PROBE_NOW stamps, written after it
+#define SSG_PROBE_WAVE_BEGIN() unsigned long long probe_own = 0, probe_bar = 0
+#define SSG_PROBE_STEP(t0, t1, t2) do { probe_own += (t1) - (t0); probe_bar += (t2) - (t1); } while (0)
+#define SSG_PROBE_WAVE_END() do { if (ssg_probe_buf_k32 && lane == 0) { ssg_probe_buf_k32[SSG_PROBE_SLOTS * blockIdx.x + 8 + 2 * wave] = probe_own; \
+                                                                      ssg_probe_buf_k32[SSG_PROBE_SLOTS * blockIdx.x + 9 + 2 * wave] = probe_bar; } } while (0)
+#define SSG_PROBE_DRAIN_STORES() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#else                                                      // the normal build: every probe macro expands to nothing
 #define SSG_STAMP(i) do { } while (0)
+#define SSG_PROBE_NOW(v) do { } while (0)
+#define SSG_PROBE_WAVE_BEGIN() do { } while (0)
+#define SSG_PROBE_STEP(t0, t1, t2) do { } while (0)
+#define SSG_PROBE_WAVE_END() do { } while (0)
+#define SSG_PROBE_DRAIN_STORES() do { } while (0)
 #endif
 
 // XF: the input is act(in1 * in_scale[c] + in_shift[c]) (ssg_conv_desc.in_scale: the batch-norm apply between conv1 and conv2 of a
@@ -202,50 +212,21 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 8) ? 
   write_px();
   SSG_STAMP(1);
 
-#ifdef SSG_K32_PROBE
-  unsigned long long probe_own = 0, probe_bar = 0;
-#endif
+  SSG_PROBE_WAVE_BEGIN();
   for (int chunk = 0; chunk < nchunks; ++chunk) {
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
       const int s = chunk * 9 + t;
-#ifndef SSG_K32_MIDBAR
-#define SSG_K32_MIDBAR 0                                   // 1: the step's barrier sits in the MIDDLE of its MFMA stream (below); 0: at the top.  Measured equal (same-box A/B, +-0.5 % on five shapes): kept as a build switch
-#endif
-#if SSG_K32_MIDBAR
-      // The barrier that makes a weight stage visible does not have to sit where the stage is first read.  The per-wave stamps of the
-      // top-of-step form (tools/k32_probe.py) show the two waves of a SIMD running one AFTER the other (waves 0-3 finish their 96
-      // MFMAs and sit ~1 500 cycles in the barrier while waves 4-7 run theirs), so behind a top-of-step barrier every wave reads its
-      // fragments at once and the matrix pipe idles until the first of them land.  Here the barrier for stage s + 1 is arrived at after
-      // the first half of step s's MFMAs: a wave that comes out of it still has half a step of MFMAs queued, and the fast wave of a
-      // SIMD reads its next fragments while the slow one multiplies.  Stage s itself was made visible by the barrier in the middle of
-      // step s - 1; the slot the pieces of step s + 2 overwrite (stage s - 1) was last read at the top of step s - 1, before that
-      // barrier, by every wave.  Only the top of a chunk keeps a barrier of its own: the rewritten pixel image (and, for chunk 0, the
-      // first stage) must be visible before tap 0 reads it -- every wave has passed the middle of tap 8, i.e. its last reads of the
-      // old image, when the first wave writes.
-      if (t == 0) {
-        if (chunk > 0) write_px();
-        wait_vmcnt<B_PC>();
-        wait_lds_reads();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      }
-#else
-#ifdef SSG_K32_PROBE
+      // the step's barrier sits at the top of the step.  In the MIDDLE of its MFMA stream it measured equal (same-box A/B, +-0.5 % on five shapes)
       SSG_PROBE_NOW(pb0);
-#endif
       if (t == LD_T + 1 || t == LD_T + 2) wait_vmcnt<B_PC + NLD>();      // the pixel loads issued at LD_T may still be in flight
       else wait_vmcnt<B_PC>();
       wait_lds_reads();
-#ifdef SSG_K32_PROBE
       SSG_PROBE_NOW(pb1);
-#endif
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-#ifdef SSG_K32_PROBE
       SSG_PROBE_NOW(pb2);
-      probe_own += pb1 - pb0; probe_bar += pb2 - pb1;
-#endif
+      SSG_PROBE_STEP(pb0, pb1, pb2);
       if (t == 0 && chunk > 0) {
         // every wave has left the last tap of the previous chunk: replace the image
         write_px();
@@ -253,11 +234,8 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 8) ? 
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }
-#endif
-#ifndef SSG_K32_DMA_MID
-#define SSG_K32_DMA_MID 1                                  // 1: the step's DMA / pixel loads are issued in the middle of its MFMA stream (A/B build switch)
-#endif
-      constexpr bool MID = SSG_K32_DMA_MID && TH != 16;   // <16, 64> keeps them at the top: pinned mid-stream, its ten pixel loads per lane spill 15-23 registers
+      // the step's DMA / pixel loads are issued in the middle of its MFMA stream (below)
+      constexpr bool MID = TH != 16;                      // <16, 64> keeps them at the top: pinned mid-stream, its ten pixel loads per lane spill 15-23 registers
       if constexpr (!MID) {
         issue_b(s + 2);
         if (t == LD_T) load_px(chunk + 1);
@@ -267,21 +245,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 8) ? 
       const int toff = (((tb & 7) - 2) * HW + ((tb >> 3) - 2)) * 16;
       const unsigned char* st = ring + (t % 3) * BSTG + wfrag;            // s % 3 == t % 3 (9 steps per chunk)
       bf16x8 p[MI][3], w[NI][3];
-#ifndef SSG_K32_READ_ORDER
-#define SSG_K32_READ_ORDER 0                               // 1: fragments are read in the order the six product terms consume them (A/B build switch: +-0 on <8,128>, 31 spills on <16,64>)
-#endif
-#if SSG_K32_READ_ORDER
-      // LDS returns reads in order and all eight waves read at once behind the barrier: the planes of the first term (w3, p1) first, so
-      // that its MFMAs start after a third of the burst instead of all of it
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const int qp = r, qw = 2 - r;                    // term order: (w3, p1), (w2, p2), (w1, p3), ...
-#pragma unroll
-        for (int i = 0; i < MI; ++i) p[i][qp] = *(const bf16x8*)(img + qp * PLANE + pb[i] + toff);
-#pragma unroll
-        for (int j = 0; j < NI; ++j) w[j][qw] = *(const bf16x8*)(st + (j * 3 + qw) * 1024);
-      }
-#else
+      // plane order.  (Reading the fragments in the order the six product terms consume them was +-0 on <8,128> and 31 spills on <16,64>.)
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -290,14 +254,11 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 8) ? 
       for (int j = 0; j < NI; ++j)
 #pragma unroll
         for (int q = 0; q < 3; ++q) w[j][q] = *(const bf16x8*)(st + (j * 3 + q) * 1024);
-#endif
-#ifndef SSG_K32_DYNPRIO
-#define SSG_K32_DYNPRIO 1                                  // 1: a wave's priority falls as it advances through a step (A/B build switch: +1 % on the <8,128> shapes, the older wave's barrier wait 1 500 -> 700 cycles per step)
-#endif
-      // The stamps show the older wave of each SIMD pair finishing its 96 MFMAs ~1 500 cycles before the younger one, which then
-      // multiplies alone -- and a lone wave issues a 16-pass MFMA only every other slot.  Priority by progress instead of by age: a wave
+      // A wave's priority falls as it advances through a step (+1 % on the <8,128> shapes, the older wave's barrier wait 1 500 -> 700 cycles per step).
+      // The stamps showed the older wave of each SIMD pair finishing its 96 MFMAs ~1 500 cycles before the younger one, which then
+      // multiplied alone -- and a lone wave issues a 16-pass MFMA only every other slot.  Priority by progress instead of by age: a wave
       // early in its step outranks one that is late in it, so the pair stays together.
-      if (SSG_K32_DYNPRIO) __builtin_amdgcn_s_setprio(3);
+      __builtin_amdgcn_s_setprio(3);
       // small terms first
 #define SSG_K32_TERM(QW, QP)                                                                      \
   _Pragma("unroll") for (int j = 0; j < NI; ++j)                                                  \
@@ -313,41 +274,17 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 8) ? 
         if (t == LD_T) load_px(chunk + 1);
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (SSG_K32_DYNPRIO) __builtin_amdgcn_s_setprio(2);
+      __builtin_amdgcn_s_setprio(2);
       SSG_K32_TERM(0, 2)
-#if SSG_K32_MIDBAR
-      {
-        // stage s + 1 (issued during step s - 1) has landed in this wave; in flight behind it: this step's pieces and, around LD_T, the
-        // pixel loads (issued after the pieces of step LD_T, before those of LD_T + 1)
-#ifdef SSG_K32_PROBE
-        SSG_PROBE_NOW(pb0);
-#endif
-        if (t == LD_T || t == LD_T + 1) wait_vmcnt<B_PC + NLD>();
-        else wait_vmcnt<B_PC>();
-        wait_lds_reads();
-#ifdef SSG_K32_PROBE
-        SSG_PROBE_NOW(pb1);
-#endif
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-#ifdef SSG_K32_PROBE
-        SSG_PROBE_NOW(pb2);
-        probe_own += pb1 - pb0; probe_bar += pb2 - pb1;
-#endif
-      }
-#endif
-      if (SSG_K32_DYNPRIO) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_s_setprio(1);
       SSG_K32_TERM(1, 0) SSG_K32_TERM(0, 1)
-      if (SSG_K32_DYNPRIO) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       SSG_K32_TERM(0, 0)
 #undef SSG_K32_TERM
       if (t == 8) {                                      // the loads of LD_T landed before tap 7's barrier
-#ifndef SSG_K32_CVT_FREE
-#define SSG_K32_CVT_FREE 1
-#endif
         // <8, 128> lets the scheduler weave the ~130 conversion instructions into tap 8's MFMAs (they fit its registers); the other
         // two tiles pin them behind the last MFMA, where the fragments are dead (woven in, <4, 64> spilled 3 registers)
-        if (!(SSG_K32_CVT_FREE && TH == 8 && !XF)) __builtin_amdgcn_sched_barrier(0);
+        if (!(TH == 8 && !XF)) __builtin_amdgcn_sched_barrier(0);
         convert_px(chunk + 1);
       }
     }
@@ -355,12 +292,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 8) ? 
   wait_vmcnt<0>();
   wait_lds_reads();
   SSG_STAMP(2);
-#ifdef SSG_K32_PROBE
-  if (ssg_probe_buf_k32 && lane == 0) {
-    ssg_probe_buf_k32[SSG_PROBE_SLOTS * blockIdx.x + 8 + 2 * wave] = probe_own;
-    ssg_probe_buf_k32[SSG_PROBE_SLOTS * blockIdx.x + 9 + 2 * wave] = probe_bar;
-  }
-#endif
+  SSG_PROBE_WAVE_END();
 
   // ---- non-finite operands (conv_slow.h): a workgroup that holds a non-finite accumulator recomputes its tile with fp32 FMAs
   {
@@ -504,11 +436,9 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 8) ? 
       dst[n0 + tid] = t1; dst[a.Cout + n0 + tid] = t2;
     }
   }
-#ifdef SSG_K32_PROBE
-  SSG_STAMP(25);                                           // every store has been issued
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the output stores have left
+  SSG_STAMP(25);                                           // (probe build) every store has been issued
+  SSG_PROBE_DRAIN_STORES();                                // the output stores have left
   SSG_STAMP(3);
-#endif
 }
 
 // fp32 packed [R][Kp] (kmode 0 with 9 taps: k = (chunk16 * 9 + tap) * 16 + c) -> [R / BN][chunk32 * 9 + tap][BN / 16 fragments][3 planes][64 lanes][16 B]:
@@ -541,8 +471,7 @@ int launch(const ConvArgs& a0, hipStream_t st) {
   constexpr int HR = (TH + 2) * 34, NPIX = (HR + 15) / 16 * 16;
   a.tiles_x = (a.GW + 31) / 32;
   a.tiles_y = (a.GH + TH - 1) / TH;
-  static const int swz = [] { const char* e = getenv("SSG_XCD_SWIZZLE"); return e ? atoi(e) : 1; }();
-  a.xcd_swizzle = swz;
+  a.xcd_swizzle = ssg_xcd_swizzle();
   a.ntiles_n = (a.Cout + BN - 1) / BN;                    // narrow tiles (BN 16 / 32): the last columns may be padding
   dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N * a.ntiles_n));
   constexpr int lds_bytes = (3 * 4 * (NPIX * 16 + 64) + 1023) / 1024 * 1024 + 3 * BN * 192 + 1024;
@@ -590,9 +519,8 @@ int ssg_conv_halo_k32_fmt(const ConvArgs& a) {
     // narrow layers (SPADE's x -> segmentation-map convs: 512 -> 16 at 128^2, 768 -> 24 at 64^2): 8 x 32-pixel tiles, all output
     // channels in one 16- or 32-column tile, 256 threads.  Two LDS fragment reads per four MFMAs instead of one: the LDS pipe is the
     // bound, at several times the rate of the fp32 256 x 32 register kernel these shapes ran on (41-44 TFLOP/s).
-    static const int narrow = [] { const char* e = getenv("SSG_K32_NARROW"); return e ? atoi(e) : 1; }();
     const long long wgs = (long long)a.N * ((a.GH + 7) / 8) * ((a.GW + 31) / 32);
-    if (!narrow || a.Cout < 12 || (a.Cout & 3) || a.C1 + a.C2 < 128) return 0;
+    if (a.Cout < 12 || (a.Cout & 3) || a.C1 + a.C2 < 128) return 0;
     return (on == 2 || wgs >= 192) ? (a.Cout <= 16 ? 1016 : 1032) : 0;
   }
   if (a.Cout % 128 == 0) {
@@ -601,9 +529,8 @@ int ssg_conv_halo_k32_fmt(const ConvArgs& a) {
     if (on == 2 || wgs >= 2048 || (wgs >= 256 && wgs * 10 >= waves * 256 * 8)) return 1128;   // >= 80 % of the last wave of tiles filled
   }
   if (a.Cout % 64 == 0) {
-    static const int t16 = [] { const char* e = getenv("SSG_K32_T16"); return e ? atoi(e) : 1; }();
     const long long wgs16 = (long long)a.N * ((a.GH + 15) / 16) * ((a.GW + 31) / 32) * (a.Cout / 64);
-    if (t16 && !a.in_scale && a.GH >= 16 && (wgs16 >= 2048 || (on == 2 && a.GH % 16 == 0))) return 2064;   // (with the fused input transform the 16-row tile spills: those launches take <4,64>)   // 16 x 32-pixel x 64-channel tiles, 512 threads (same pack as 1064)
+    if (!a.in_scale && a.GH >= 16 && (wgs16 >= 2048 || (on == 2 && a.GH % 16 == 0))) return 2064;   // (with the fused input transform the 16-row tile spills: those launches take <4,64>)   // 16 x 32-pixel x 64-channel tiles, 512 threads (same pack as 1064)
     const long long wgs = (long long)a.N * ((a.GH + 3) / 4) * ((a.GW + 31) / 32) * (a.Cout / 64);
     if (on == 2 || wgs >= 1536) return 1064;
   }

@@ -14,11 +14,6 @@
 // Same descriptor contract as ssg_conv2d_igemm_f32 (bias, residual, activation, pad lanes written as 0).
 #include "common.h"
 #include "conv_thin.h"
-#ifndef SSG_T4_EXP
-#define SSG_T4_EXP 0      // 1 = no MFMAs, 2 = no output stores: ablation builds of thin4_cin; 3 = no MFMAs, 4 = cache-resident loads:
-                          // of thin4_cout (tools/micro_thin_exp.py), never shipped
-#endif
-#include <stdlib.h>
 
 namespace {
 
@@ -131,13 +126,9 @@ __global__ __launch_bounds__(256) void thin4_cin_kernel(const T4Args a) {
         if (y + r < y1) {
           // The previous row's result is stored here, a whole MFMA phase before the next s_waitcnt has to
           // cover it (gfx9 counts stores in vmcnt: a store issued right before the wait exposes its latency).
-#if SSG_T4_EXP == 2
-          if (pend_ptr && pend[0] == 123.456f) *(f32x4*)pend_ptr = pend;          // ablation: no output stores
-#else
           // outputs far larger than the caches (the 1-GB gamma / beta buffers of the 512^2 level) are stored non-temporally:
-          // 0.474 -> 0.402 ms on 16 x 512^2, 4 -> 64 (tools/micro_thin_exp.py)
+          // 0.474 -> 0.402 ms on 16 x 512^2, 4 -> 64
           if (pend_ptr) { if (a.nt_store) __builtin_nontemporal_store(pend, (f32x4*)pend_ptr); else *(f32x4*)pend_ptr = pend; }
-#endif
           // row (y + r) + R + PF goes into the slot of row (y + r) - R - 1, whose last reader was the previous iteration
           load_row(v[(r + KS + PF - 1) % RING], y + r - R + KS + PF - 1);
           const size_t pix = (size_t)(n * a.H + y + r) * a.W + x;
@@ -145,9 +136,6 @@ __global__ __launch_bounds__(256) void thin4_cin_kernel(const T4Args a) {
           if (HAS_RES) { rvr[(r + 1) % RING] = load_res(y + r + 1); rv = rvr[r]; }
           // two accumulator chains (even / odd k) keep dependent MFMAs apart
           f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#if SSG_T4_EXP == 1
-          acc0 = v[r % RING][0] + v[(r + KS - 1) % RING][KS - 1];                  // ablation: no MFMAs (rows stay live)
-#else
 #pragma unroll
           for (int q = 0; q < KS; ++q)
 #pragma unroll
@@ -157,7 +145,6 @@ __global__ __launch_bounds__(256) void thin4_cin_kernel(const T4Args a) {
                 acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[q * KS + e][c], v[(r + q) % RING][e][c], acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[q * KS + e][c + 1], v[(r + q) % RING][e][c + 1], acc1, 0, 0, 0);
               }
-#endif
           const f32x4 t = acc0 + acc1 + bv + rv * cmask;
 #pragma unroll
           for (int i = 0; i < 4; ++i) pend[i] = (t[i] < 0.f ? (is_relu ? 0.f : t[i] * neg_slope) : t[i]) * cmask[i];
@@ -171,7 +158,7 @@ __global__ __launch_bounds__(256) void thin4_cin_kernel(const T4Args a) {
 
 // ------------------------------------------------------------------ thin-Cin on the 32x32x2 MFMA: C == 4, 3x3 window, Cout >= 32
 // The 4x4x1 kernel above issues 36 MFMAs + ~90 other instructions per 1 KiB of output and is bound by instruction issue
-// (tools/micro_thin_exp.py: 0.30 ms of its 0.40 ms at 16 x 512^2, 4 -> 64, remain with the stores compiled out).  K = 9 taps x
+// (an ablation build measured it: 0.30 ms of its 0.40 ms at 16 x 512^2, 4 -> 64, remained with the stores compiled out).  K = 9 taps x
 // 4 channels = 36 is exactly 18 K-steps of v_mfma_f32_32x32x2_f32, so the same FLOPs take 8x fewer MFMA instructions as a
 // plain GEMM: M = 32 consecutive pixels of one image row (lane&31), N = 2 x 32 output channels, and the lane half (lane>>5)
 // picks the channel pair {2h, 2h+1} of a tap -- one 8-byte load per (input row, dx) and lane, every input row loaded once per
@@ -539,16 +526,8 @@ __global__ __launch_bounds__(256) void thin4_cout_kernel(const T4Args a) {
       auto load_row = [&](f32x4* dst, int iy) {
         const bool rok = (unsigned)iy < (unsigned)a.H;
         const unsigned ro = imgoff + (unsigned)iy * (unsigned)a.W * ldb + (unsigned)ch * 256u;
-#if SSG_T4_EXP == 4                                        // ablation: every row load reads the same cache-resident 1 KiB
-#pragma unroll
-        for (int e = 0; e < KS; ++e) dst[e] = ldbuf4(in_rs, (rok && coloff[e] != OOB) ? (unsigned)(lane * 16) : OOB);
-#elif SSG_T4_EXP == 5                                      // ablation: only the dx = 0 load is real, dx = +-1 read that KiB
-#pragma unroll
-        for (int e = 0; e < KS; ++e) dst[e] = ldbuf4(in_rs, (rok && coloff[e] != OOB) ? (e == R ? ro + coloff[e] : (unsigned)(lane * 16)) : OOB);
-#else
 #pragma unroll
         for (int e = 0; e < KS; ++e) dst[e] = ldbuf4(in_rs, (rok && coloff[e] != OOB) ? ro + coloff[e] : OOB);
-#endif
       };
       f32x4 v[RING][KS];
 #pragma unroll
@@ -564,11 +543,7 @@ __global__ __launch_bounds__(256) void thin4_cout_kernel(const T4Args a) {
             for (int c = 0; c < 4; ++c)
 #pragma unroll
               for (int g = 0; g < NG; ++g) {
-#if SSG_T4_EXP == 3                                        // ablation: no MFMAs (loaded rows stay live through one add per value)
-                accg[g][s][c] += v[(s + q) % RING][e][c];
-#else
                 accg[g][s] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[g][q * KS + e][c], v[(s + q) % RING][e][c], accg[g][s], 0, 0, 0);
-#endif
               }
       }
     }
@@ -579,7 +554,7 @@ __global__ __launch_bounds__(256) void thin4_cout_kernel(const T4Args a) {
 
 // (A streaming form of this kernel -- a wave walking a column of bands with all 10 rows of a body in a register ring, every row
 //  requested a whole body before its first use -- was built and measured in round 2: 0.580 vs 0.585 ms at 16 x 512^2, 64 -> 3.
-//  Ablations (tools/micro_thin_cout.py): no MFMAs 0.520, every load from one cache-resident KiB 0.319, only the dx = 0 loads
+//  Ablation builds: no MFMAs 0.520, every load from one cache-resident KiB 0.319, only the dx = 0 loads
 //  real 0.480: the time is issue (0.32) PLUS memory (0.16 unique + 0.10 for the overlapping dx loads), not latency.)
 
 bool window_taps(const ssg_conv_desc* d, int* tapidx) {
@@ -596,15 +571,9 @@ bool window_taps(const ssg_conv_desc* d, int* tapidx) {
   return true;
 }
 
-int thin4_on() {
-  static const int on = [] { const char* e = getenv("SSG_THIN4"); return e ? atoi(e) : 3; }();
-  return on;
-}
-
 }  // namespace
 
-// 0 = no; 3 = thin-Cin (in has 4 channels); 4 = thin-Cout (Cout <= 8, Cin % 64 == 0).  SSG_THIN4 is a bit
-// mask (1 = thin-Cin, 2 = thin-Cout; default both).
+// 0 = no; 3 = thin-Cin (in has 4 channels); 4 = thin-Cout (Cout <= 8, Cin % 64 == 0).
 int ssg_thin4_conv_kind(const ssg_conv_desc* d) {
   if (d->C2 != 0 || d->in_sy != 1 || d->in_sx != 1 || d->out_sy != 1 || d->out_sx != 1 || d->out_oy || d->out_ox) return 0;
   if (d->GH != d->H || d->GW != d->W || d->OH != d->H || d->OW != d->W) return 0;
@@ -612,20 +581,18 @@ int ssg_thin4_conv_kind(const ssg_conv_desc* d) {
   if (((uintptr_t)d->in1 & 15) || d->ld1 % 4 || ((uintptr_t)d->w & 15) || d->Kp % 4) return 0;
   int tapidx[9];
   if (!window_taps(d, tapidx)) return 0;
-  if ((thin4_on() & 1) && d->C1 == 4 && d->kmode == 1 && d->ldo % 4 == 0 && !((uintptr_t)d->out & 15) &&
+  if (d->C1 == 4 && d->kmode == 1 && d->ldo % 4 == 0 && !((uintptr_t)d->out & 15) &&
       (!d->res || (d->ldr % 4 == 0 && !((uintptr_t)d->res & 15) && (long long)d->N * d->H * d->W * d->ldr < (1ll << 30)))) return 3;
-  if ((thin4_on() & 2) && d->Cout <= 8 && d->C1 >= 64 && d->C1 % 64 == 0 && d->ldo % 2 == 0 && !((uintptr_t)d->out & 7)) return 4;
+  if (d->Cout <= 8 && d->C1 >= 64 && d->C1 % 64 == 0 && d->ldo % 2 == 0 && !((uintptr_t)d->out & 7)) return 4;
   return 0;
 }
 
 static bool routes_tiny(const ssg_conv_desc* d, int kind) {
-  static const int tiny = [] { const char* e = getenv("SSG_TINY4"); return e ? atoi(e) : 1; }();       // 0: 4x4x1 kernel (A/B switch)
-  return kind == 3 && tiny && d->Cout <= 8 && (long long)d->N * d->H * d->W * d->ld1 < (1ll << 30);
+  return kind == 3 && d->Cout <= 8 && (long long)d->N * d->H * d->W * d->ld1 < (1ll << 30);
 }
 
 static bool routes_thin32(const ssg_conv_desc* d, int kind) {
-  static const int k36 = [] { const char* e = getenv("SSG_THIN32"); return e ? atoi(e) : 1; }();       // 0: 4x4x1 kernel (A/B switch)
-  if (kind != 3 || !k36 || d->Cout < 32 || (long long)d->N * d->H * d->W * d->ldo >= (1ll << 30)) return false;
+  if (kind != 3 || d->Cout < 32 || (long long)d->N * d->H * d->W * d->ldo >= (1ll << 30)) return false;
   if (d->W < 32 || (long long)d->N * d->H * d->W < 65536) return false;          // 32-pixel strips: small images stay on the 4-pixel kernel
   for (int t = 0; t < d->ntaps; ++t) if (d->dy[t] || d->dx[t]) return true;       // a real window, not the 1x1 case
   return false;
@@ -673,8 +640,7 @@ int ssg_thin4_conv_launch(const ssg_conv_desc* d, int kind, hipStream_t st) {
     if (wpg2 > a.total_units) wpg2 = a.total_units;
     a.waves_per_group = wpg2;
     const dim3 grid2((unsigned)((wpg2 * a.groups + 3) / 4));
-    static const int nt32 = [] { const char* e = getenv("SSG_THIN32_NT"); return e ? atoi(e) : 1; }();
-    const bool nt = nt32 && a.nt_store;
+    const bool nt = a.nt_store;
     if (d->res) {
       if (nt) hipLaunchKernelGGL((thin32_cin_kernel<1, 1, true>), grid2, block, 0, st, a);
       else hipLaunchKernelGGL((thin32_cin_kernel<1, 1, false>), grid2, block, 0, st, a);
@@ -686,14 +652,11 @@ int ssg_thin4_conv_launch(const ssg_conv_desc* d, int kind, hipStream_t st) {
     return SSG_OK;
   }
   if (kind == 3) {
-    static const int pf = [] { const char* e = getenv("SSG_THIN4_PF"); return e ? atoi(e) : 2; }();     // rows in flight (A/B switch)
     if (d->res) {
       if (ks1) hipLaunchKernelGGL((thin4_cin_kernel<1, 1, true>), grid, block, 0, st, a);
       else hipLaunchKernelGGL((thin4_cin_kernel<3, 1, true>), grid, block, 0, st, a);
     } else if (ks1) hipLaunchKernelGGL((thin4_cin_kernel<1, 2, false>), grid, block, 0, st, a);
-    else if (pf <= 1) hipLaunchKernelGGL((thin4_cin_kernel<3, 1, false>), grid, block, 0, st, a);
-    else if (pf == 2) hipLaunchKernelGGL((thin4_cin_kernel<3, 2, false>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((thin4_cin_kernel<3, 4, false>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((thin4_cin_kernel<3, 2, false>), grid, block, 0, st, a);     // two rows in flight (one and four measured equal)
   } else {
     if (d->Cout <= 4) {
       if (ks1) hipLaunchKernelGGL((thin4_cout_kernel<1, 1>), grid, block, 0, st, a);
@@ -710,8 +673,7 @@ int ssg_thin4_conv_launch(const ssg_conv_desc* d, int kind, hipStream_t st) {
 // ------------------------------------------------------------------ SPADE: gamma|beta conv + modulation in one kernel
 // 4 = the 4-channel-input kernel, 8 = the 8-channel one, 0 = not handled
 static int spade_fused_cin(const ssg_conv_desc* d) {
-  static const int on = [] { const char* e = getenv("SSG_SPADE_FUSED"); return e ? atoi(e) : 1; }();     // 0: conv + modulate pass (A/B); 4: only the 4-channel form
-  if (!on || !d || d->res || d->act != SSG_ACT_NONE || d->bnpart || (d->Cout & 7) || d->ntaps != 9 || d->kmode != 1) return 0;
+  if (!d || d->res || d->act != SSG_ACT_NONE || d->bnpart || (d->Cout & 7) || d->ntaps != 9 || d->kmode != 1) return 0;
   if (d->C2 != 0 || d->in_sy != 1 || d->in_sx != 1 || d->out_sy != 1 || d->out_sx != 1 || d->out_oy || d->out_ox) return 0;
   if (d->GH != d->H || d->GW != d->W || d->OH != d->H || d->OW != d->W) return 0;
   if (((uintptr_t)d->in1 & 15) || d->ld1 % 4 || ((uintptr_t)d->w & 15) || d->Kp % 4 || d->ldo % 4 || ((uintptr_t)d->out & 15)) return 0;
@@ -720,7 +682,7 @@ static int spade_fused_cin(const ssg_conv_desc* d) {
   if (d->W < 32 || (long long)d->N * d->H * d->W < 65536) return 0;
   if ((long long)d->N * d->H * d->W * (d->Cout / 2) >= (1ll << 30) || (long long)d->N * d->H * d->W * d->ld1 >= (1ll << 30)) return 0;
   if (d->C1 == 4) return 4;
-  if (d->C1 == 8 && on != 4) return 8;
+  if (d->C1 == 8) return 8;
   return 0;
 }
 

@@ -11,7 +11,6 @@
 #include "common.h"
 #include "conv_thin.h"
 #include "conv_wgrad_args.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -182,27 +181,16 @@ __global__ __launch_bounds__(32 * ZL) void wgrad_reduce_kernel(const RedArgs a) 
 enum { WG_MFMA, WG_HALO, WG_K32, WG_4 };
 struct Plan { int variant, mt, nt, splits, steps_per_split, kind; };
 
-// thin weight gradients on the 4x4x1 MFMA (conv_wgrad4.hip); SSG_WGRAD4=0 switches them off (A/B)
-int wgrad4_kind(const ssg_wgrad_desc* d) {
-  static const int on = [] { const char* e = getenv("SSG_WGRAD4"); return e ? atoi(e) : 1; }();
-  return on ? ssg_wgrad4_kind(d) : 0;
-}
+// LDS-DMA pipeline (conv_wgrad_dma.hip) for Cout > 32; the 32-column tile stays on the register-staged kernel
+bool wgrad_uses_dma(int variant) { return variant <= 1; }
 
-bool wgrad_uses_dma(int variant) {
-  static const int use_dma = [] { const char* e = getenv("SSG_WGRAD_DMA"); return e ? atoi(e) : 1; }();
-  return use_dma && variant <= 1;
-}
-
-// LDS-resident pixel window (conv_wgrad_halo.hip) for the 3x3 window; SSG_WGRAD_HALO=0 switches it off (A/B)
-bool wgrad_uses_halo(const ssg_wgrad_desc* d, int variant) {
-  static const int on = [] { const char* e = getenv("SSG_WGRAD_HALO"); return e ? atoi(e) : 1; }();
-  return on && variant <= 1 && wgrad_uses_dma(variant) && ssg_wgrad_halo_ok(d, variant);
-}
+// LDS-resident pixel window (conv_wgrad_halo.hip) for the 3x3 window
+bool wgrad_uses_halo(const ssg_wgrad_desc* d, int variant) { return wgrad_uses_dma(variant) && ssg_wgrad_halo_ok(d, variant); }
 
 Plan make_plan(const ssg_wgrad_desc* d) {
   Plan p;
   p.kind = WG_MFMA;
-  if (const int w4 = wgrad4_kind(d)) {
+  if (const int w4 = ssg_wgrad4_kind(d)) {     // thin weight gradients on the 4x4x1 MFMA (conv_wgrad4.hip)
     p.kind = WG_4; p.variant = w4;
     p.mt = p.nt = p.steps_per_split = 0;
     p.splits = ssg_wgrad4_slices(d, w4, nullptr, nullptr, nullptr);
@@ -247,7 +235,7 @@ Plan make_plan(const ssg_wgrad_desc* d) {
       if (chain_px / 32 < max_rows) max_rows = chain_px / 32;
       if (max_rows < 8) max_rows = 8;
     }
-    const long long lo = ssg_wgrad_k32_flush() == 0 ? (steps + max_rows - 1) / max_rows : 1;
+    const long long lo = (steps + max_rows - 1) / max_rows;
     long long hi = steps / 8;
     if (hi < lo) hi = lo;
     long long best = lo; double beff = 0;
@@ -261,8 +249,7 @@ Plan make_plan(const ssg_wgrad_desc* d) {
     p.splits = (int)((steps + p.steps_per_split - 1) / p.steps_per_split);
     return p;
   }
-  static const int wgs = [] { const char* e = getenv("SSG_WGRAD_WGS"); return e ? atoi(e) : 1024; }();
-  long long want = wgs / ((long long)p.mt * p.nt);       // ~4 workgroups per CU overall (2048: +0.4 % slab traffic time)
+  long long want = 1024 / ((long long)p.mt * p.nt);       // ~4 workgroups per CU overall (2048: +0.4 % slab traffic time)
   if (want < 1) want = 1;
   long long maxs = steps / 16;                           // at least 16 K-steps (256 pixels) per split
   if (maxs < 1) maxs = 1;
@@ -371,11 +358,8 @@ extern "C" int ssg_conv2d_wgrad_f32(const ssg_wgrad_desc* d, void* stream) {
     } else if (wgrad_uses_dma(p.variant)) {
       rc = ssg_wgrad_dma_launch(a, p.variant, grid, st, (d->flags & 1) != 0);
       if (rc != SSG_OK) return rc;
-    } else
-    switch (p.variant) {
-      case 0: hipLaunchKernelGGL((wgrad_kernel<128, 128, 2, 2>), grid, dim3(256), 0, st, a); break;
-      case 1: hipLaunchKernelGGL((wgrad_kernel<128, 64, 2, 2>), grid, dim3(256), 0, st, a); break;
-      default: hipLaunchKernelGGL((wgrad_kernel<128, 32, 4, 1>), grid, dim3(256), 0, st, a); break;
+    } else {
+      hipLaunchKernelGGL((wgrad_kernel<128, 32, 4, 1>), grid, dim3(256), 0, st, a);     // variant 2
     }
     SSG_LAUNCH_CHECK();
   }
@@ -424,7 +408,7 @@ extern "C" int ssg_pack_weights_scaled_f32(const float* w_oihw, int O, int I, in
   return SSG_OK;
 }
 
-// which kernel a wgrad descriptor maps to: 0..2 = wgrad<128,128>/<128,64>/<128,32>, 20/21 = wgrad_dma<128,128>/<128,64>, 30/31 = wgrad_halo<32,128>/<64,64>, 40/41 / 50/51 = the split-operand (x3) forms of 30/31 / 20/21, 60 = wgrad_k32 (conv_wgrad_k32.hip), 15/16 = wgrad4 (4x4x1 MFMA)
+// which kernel a wgrad descriptor maps to: 2 = wgrad<128,32> (register-staged), 20/21 = wgrad_dma<128,128>/<128,64>, 30/31 = wgrad_halo<32,128>/<64,64>, 40/41 / 50/51 = the split-operand (x3) forms of 30/31 / 20/21, 60 = wgrad_k32 (conv_wgrad_k32.hip), 15/16 = wgrad4 (4x4x1 MFMA)
 extern "C" int ssg_conv2d_wgrad_kernel_id(const ssg_wgrad_desc* d) {
   if (!d) return SSG_EINVAL;
   const Plan p = make_plan(d);

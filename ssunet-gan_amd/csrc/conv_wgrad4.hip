@@ -274,10 +274,8 @@ int ssg_wgrad4_kind(const ssg_wgrad_desc* d) {
   // 32-bit byte offsets (buffer descriptors) inside the kernel
   if ((long long)d->N * d->H * d->W * (d->ld1 > d->ldd ? d->ld1 : d->ldd) >= (1ll << 30)) return 0;
   if (d->Cout <= 4 && d->C1 >= 16 && d->C1 % 4 == 0) return 5;
-  static const int tiny = [] { const char* e = getenv("SSG_TINY4"); return e ? atoi(e) : 1; }();
-  if (tiny && d->C1 == 4 && d->Cout <= 8 && d->ntaps == 9) return 7;
-  static const int w32 = [] { const char* e = getenv("SSG_WGRAD32"); return e ? atoi(e) : 1; }();
-  if (w32 && d->C1 == 4 && d->ntaps == 9 && d->Cout >= 32 && (long long)d->N * d->H * d->W >= 65536) return 8;
+  if (d->C1 == 4 && d->Cout <= 8 && d->ntaps == 9) return 7;
+  if (d->C1 == 4 && d->ntaps == 9 && d->Cout >= 32 && (long long)d->N * d->H * d->W >= 65536) return 8;
   if (d->C1 == 4) return 6;
   return 0;
 }

@@ -225,8 +225,7 @@ __global__ __launch_bounds__(256) void wgrad_dma_x3_kernel(const WgArgs a) { wgr
 
 int ssg_wgrad_dma_launch(const WgArgs& a0, int variant, dim3 grid, hipStream_t st, bool split) {
   WgArgs a = a0;
-  static const int swz = [] { const char* e = getenv("SSG_XCD_SWIZZLE"); return e ? atoi(e) : 1; }();
-  a.xcd_swizzle = swz;
+  a.xcd_swizzle = ssg_xcd_swizzle();
   if (split) {
     if (variant == 0) hipLaunchKernelGGL((wgrad_dma_x3_kernel<128, 128>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((wgrad_dma_x3_kernel<128, 64>), grid, dim3(256), 0, st, a);

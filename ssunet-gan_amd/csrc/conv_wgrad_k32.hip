@@ -37,10 +37,6 @@ constexpr int DSLOT = KP * 128;
 constexpr int DPLANE = 2 * DSLOT;
 constexpr int DIMG = 3 * DPLANE;
 constexpr int CB = 64, BN = 64;
-#ifndef SSG_WK32_FLUSH
-#define SSG_WK32_FLUSH 0                       // > 0: rows of MFMA accumulation per flush into vector-unit totals (A/B; costs 72 registers and ~10 %); 0: the slab
-                                               // length bounds the accumulation chain instead (conv_wgrad.hip: at most 128 rows per slab)
-#endif
 
 // 16-byte chunk c (0..7) of pixel row p sits at chunk position c ^ sw(p)
 __device__ __forceinline__ int sw(int p) { return ((((p >> 1) & 1) | (((p >> 3) & 1) << 1)) << 1); }
@@ -151,16 +147,15 @@ __global__ __launch_bounds__(512, 1) void wgrad_k32_kernel(const WgArgs a) {
       doff[j][t] = p * 128 + ((((2 * (2 * wn + j) + (pp >> 1)) ^ sw(p))) << 4) + (pp & 1) * 8;
   }
 
-  // Accumulation chains: the rounding error of a slab grows with the number of pixels one accumulator sums.  Default: the planner keeps
-  // a slab at <= 128 rows (4096 pixels, wgrad_halo_x3's slab at the bench sizes; rms error vs fp64 then equals that kernel's).  With
-  // FLUSH > 0 acc takes FLUSH rows and is then added into tot by the vector unit (slabs may be long): measured 205 vs 228 TFLOP/s.
-  constexpr int FLUSH = SSG_WK32_FLUSH;
+  // Accumulation chains: the rounding error of a slab grows with the number of pixels one accumulator sums.  The planner keeps
+  // a slab at <= 128 rows (4096 pixels, wgrad_halo_x3's slab at the bench sizes; rms error vs fp64 then equals that kernel's:
+  // conv_wgrad.hip).  (A form that flushed acc into vector-unit totals every few rows, so that slabs could be long, cost 72 registers
+  // and ~10 %: measured 205 vs 228 TFLOP/s.  tot is what is left of it: acc is added into it once, after the loop.)
   f32x4 acc[9][2], tot[9][2];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int j = 0; j < 2; ++j) { acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f}; tot[t][j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  int since = 0;
 
   auto frag = [&](const unsigned char* base, int o0, int o1) -> bf16x8 {
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + o0));
@@ -195,12 +190,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_k32_kernel(const WgArgs a) {
       asm volatile("" ::: "memory");
       const bool more = gy + 1 < gb;
       RawX nx; RawD nd;
-#ifndef SSG_WK32_LOAD_MID
-#define SSG_WK32_LOAD_MID 0                                // 1: the next rows' loads go out after the first tap row's MFMAs instead of behind the barrier (A/B build switch)
-#endif
-#if !SSG_WK32_LOAD_MID
-      if (more) { nx = load_x(n, gy + 2, gx0); nd = load_d(n, gy + 1, gx0); }
-#endif
+      if (more) { nx = load_x(n, gy + 2, gx0); nd = load_d(n, gy + 1, gx0); }      // behind the barrier (after the first tap row's MFMAs instead: no gain)
 
       const unsigned char* db = dimg + (gy & 1) * DSLOT;
       bf16x8 df[2][3];
@@ -210,10 +200,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_k32_kernel(const WgArgs a) {
         for (int q = 0; q < 3; ++q) df[j][q] = frag(db + q * DPLANE, doff[j][0], doff[j][1]);
 #pragma unroll
       for (int dyi = 0; dyi < 3; ++dyi) {
-#ifndef SSG_WK32_DYNPRIO
-#define SSG_WK32_DYNPRIO 1                                 // 1: a wave's priority falls as it advances through a step (as conv_halo_k32_kernel; A/B build switch)
-#endif
-        if (SSG_WK32_DYNPRIO) { if (dyi == 0) __builtin_amdgcn_s_setprio(3); else if (dyi == 1) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1); }
+        // a wave's priority falls as it advances through a step (as conv_halo_k32_kernel)
+        { if (dyi == 0) __builtin_amdgcn_s_setprio(3); else if (dyi == 1) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1); }
         const unsigned char* xb = ximg + ((gy + dyi) & 3) * XSLOT;        // row gy - 1 + dyi -> slot (row + 1) & 3
         bf16x8 xf[3][3];
 #pragma unroll
@@ -229,26 +217,12 @@ __global__ __launch_bounds__(512, 1) void wgrad_k32_kernel(const WgArgs a) {
         SSG_WK_TERM(1, 0) SSG_WK_TERM(0, 1)
         SSG_WK_TERM(0, 0)
 #undef SSG_WK_TERM
-#if SSG_WK32_LOAD_MID
-        if (dyi == 0) {
-          __builtin_amdgcn_sched_barrier(0);
-          if (more) { nx = load_x(n, gy + 2, gx0); nd = load_d(n, gy + 1, gx0); }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-#endif
       }
-      if (SSG_WK32_DYNPRIO) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       if (more) {
         __builtin_amdgcn_sched_barrier(0);
         store_x(nx, (gy + 3) & 3, gy + 2, gx0);         // row gy + 2
         store_d(nd, (gy + 1) & 1);
-      }
-      if (FLUSH > 0 && ++since == FLUSH) {
-        since = 0;
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) { tot[t][j] += acc[t][j]; acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
       }
     }
     S = Se;
@@ -312,8 +286,6 @@ bool ssg_wgrad_k32_ok(const ssg_wgrad_desc* d) {
   const unsigned long long db = (unsigned long long)d->N * d->GH * d->GW * (unsigned long long)d->ldd * 4ull;
   return xb <= 0xfffffff0ull && db <= 0xfffffff0ull;
 }
-
-int ssg_wgrad_k32_flush() { return SSG_WK32_FLUSH; }
 
 // K-steps of the k32 kernel: one per image row of each 32-pixel column strip
 long long ssg_wgrad_k32_steps(const ssg_wgrad_desc* d) { return (long long)d->N * ((d->GW + KP - 1) / KP) * d->GH; }

@@ -371,8 +371,7 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restri
 
 // streaming bilinear kernels: 16-channel tiles, scales in [0.4, 0.5) on both axes (H, W >= 3), a grid that fits 32 bits
 static bool bilinear_stream_ok(int N, int H, int W, int C) {
-  static const int on = [] { const char* e = getenv("SSG_BILINEAR_STREAM"); return e ? atoi(e) : 1; }();
-  return on && C % 16 == 0 && H >= 3 && W >= 3 && (long long)N * (2 * H / BIL_FWD_BAND + 1) * (2 * W / 16 + 1) * (C / 16) < (1ll << 31);
+  return C % 16 == 0 && H >= 3 && W >= 3 && (long long)N * (2 * H / BIL_FWD_BAND + 1) * (2 * W / 16 + 1) * (C / 16) < (1ll << 31);
 }
 #define REQ_Q(C, ...) SSG_REQUIRE((C) > 0 && (C) % 4 == 0, SSG_EINVAL, __VA_ARGS__)
 

@@ -1,7 +1,5 @@
 """MBConvBlock and the EfficientNet feature extractor on the HIP kernels (mirrors
 efficientnet_pytorch/model.py:18-99,132-218 of the reference; parameter names and creation order kept)."""
-import os
-
 import torch
 import torch.nn as nn
 
@@ -9,10 +7,6 @@ from .. import bf16, ops
 from .._lib import ACT_SWISH
 from .utils import (MemoryEfficientSwish, Swish, drop_connect, get_model_params, get_same_padding_conv2d, round_filters,
                     round_repeats)
-
-
-# SSG_BF16_STEM=0: in bf16 mode the stem stays an fp32 conv + fp32 batch norm followed by a conversion (rounds 2-3)
-BF16_STEM = os.environ.get('SSG_BF16_STEM', '1') != '0'
 
 
 class MBConvBlock(nn.Module):
@@ -156,7 +150,7 @@ class EfficientNet(nn.Module):
     def extract_features(self, inputs):
         lowp = getattr(self, '_ssg_dtype', torch.float32) == torch.bfloat16
         stem = self._conv_stem
-        if lowp and BF16_STEM and stem.bias is None and stem.out_channels % 8 == 0:
+        if lowp and stem.bias is None and stem.out_channels % 8 == 0:
             # the stem in the bf16 family too (csrc/conv_stem_bf16.hip): bf16-rounded image and weights, fp32 accumulation, bf16 output
             x = bf16.batch_norm_act(bf16.conv_thin(ops.as_nhwc(inputs), stem.weight, stem.stride[0], stem.static_pad), self._bn0, act=ACT_SWISH)
         else:

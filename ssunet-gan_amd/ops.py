@@ -320,7 +320,7 @@ def _conv_launch(x1, x2, wpk, kp, kmode, row0, cout, bias, res, act, slope, taps
         if not call('ssg_conv2d_bwd_stats_ok', C.byref(d)):
             raise _Declined()
         want_bn = True
-    rows = call('ssg_conv2d_bnpart_rows', C.byref(d)) if want_bn and BN_EPILOGUE else 0
+    rows = call('ssg_conv2d_bnpart_rows', C.byref(d)) if want_bn else 0
     if bwd_stats is not None and rows == 0:
         raise _Declined()
     split = _split_pack(wpk, row0, cout, kp, pack) if pack else None
@@ -346,9 +346,7 @@ def _conv_launch(x1, x2, wpk, kp, kmode, row0, cout, bias, res, act, slope, taps
     return part
 
 
-# SSG_BN_EPILOGUE=0: batch-norm statistics from their own pass over the conv output instead of the conv epilogue (A/B switch)
 import os as _os
-BN_EPILOGUE = _os.environ.get('SSG_BN_EPILOGUE', '1') != '0'
 # The dense 3x3 unit-stride convs and their input gradients multiply on the bf16 matrix pipe with every fp32 operand split into
 # three bf16 terms (csrc/conv_igemm_halo_x3.hip: the error against fp64 is that of the fp32-MFMA kernel, tests/test_split_gpu.py;
 # 16/6 of the fp32 MFMA rate).  SSG_MFMA_SPLIT=0 keeps them on v_mfma_f32_32x32x2_f32 (conv_igemm_halo.hip).
@@ -452,7 +450,7 @@ def _conv_dgrad_impl(dy, weight, stride, pad, h, w, c_lo, c_hi, res=None, wscale
     # than 17 pixels, channel counts that are not whole 64-column tiles and tensors beyond 32-bit byte offsets
     # (ssg_conv_halo_x3_parity_ok); with spectral norm a declined pack would be an uncached launch + allocation per backward
     if (PARITY_MERGE and s == 2 and kh == 3 and kw == 3 and (pt, pl) == (1, 1) and MFMA_SPLIT and ow >= 17
-            and (c_hi - c_lo) % 64 == 0 and dy.numel() * 4 <= 0xfffffff0 and _os.environ.get('SSG_X3_PARITY', '1') != '0'):
+            and (c_hi - c_lo) % 64 == 0 and dy.numel() * 4 <= 0xfffffff0):
         # the four classes read the same 2x2 neighbourhood of dy: one launch, nine tap steps, four accumulator sets
         # (conv_igemm_halo_x3_kernel<..., PARITY>); falls through to the per-class launches where the library declines
         merged = [t for _, _, taps in classes for t in taps]
@@ -1421,9 +1419,6 @@ def global_avgpool(x):
     return _GlobalAvgPool.apply(x)
 
 
-SE_FUSED = _os.environ.get('SSG_SE_FUSED', '1') != '0'
-
-
 class _SEGate(torch.autograd.Function):
     """sigmoid(_se_expand(swish(_se_reduce(sq)))) on the pooled [N, C, 1, 1] vector (efficientnet_pytorch/model.py:84-86) as
     2 kernels forward and 3 backward (csrc/se_gate.hip) instead of two 1x1 conv launches with their packs, activations,
@@ -1468,7 +1463,7 @@ def se_gate(sq, reduce_conv, expand_conv):
     _lib.require_gpu(sq)
     w1, w2 = reduce_conv.weight, expand_conv.weight
     n, c = sq.shape[0], sq.shape[1]
-    if not SE_FUSED or tuple(w1.shape[1:]) != (c, 1, 1) or tuple(w2.shape) != (c, w1.shape[0], 1, 1) or sq.dtype != torch.float32:
+    if tuple(w1.shape[1:]) != (c, 1, 1) or tuple(w2.shape) != (c, w1.shape[0], 1, 1) or sq.dtype != torch.float32:
         return None
     if not call('ssg_se_gate_ok', n, c, w1.shape[0]):
         return None

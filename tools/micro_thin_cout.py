@@ -1,5 +1,5 @@
-"""thin4_cout (wide input, <= 8 output channels) against its ablation builds libssunet_exp{3,4}.so (-DSSG_T4_EXP=3: no MFMAs,
-4: every row load hits the same cache-resident KiB); built like tools/micro_thin_exp.py describes."""
+"""thin4_cout (wide input, <= 8 output channels) at 16 images: the shipped library, then any other builds of it named on the
+command line (file names under ssunet-gan_amd/, loaded through SSG_LIB_PATH).  Usage: python tools/micro_thin_cout.py [lib.so ...]"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = r'''
@@ -25,7 +25,7 @@ for (ci, co, hw) in [(64, 3, 512), (128, 4, 512), (256, 8, 256)]:
     out.append('%%d->%%d@%%d %%.3f ms %%.2f TB/s' %% (ci, co, hw, ms, 16 * hw * hw * 4 * (ci + 4) / ms / 1e9))
 print('%%-20s %%s' %% (os.path.basename(os.environ.get('SSG_LIB_PATH', 'shipped')), ' | '.join(out)))
 ''' % ROOT
-for lib in [None] + ['libssunet_exp%s.so' % a for a in sys.argv[1:]]:
+for lib in [None] + sys.argv[1:]:
     env = dict(os.environ)
     if lib:
         env['SSG_LIB_PATH'] = os.path.join(ROOT, 'ssunet-gan_amd', lib)
