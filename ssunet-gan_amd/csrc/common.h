@@ -107,6 +107,24 @@ __device__ __forceinline__ unsigned ssg_xcd_band(unsigned id, unsigned n) {
   const unsigned per = n >> 3, rem = n & 7u, k = id & 7u;
   return k * per + (k < rem ? k : rem) + (id >> 3);
 }
+// The conv / GEMM tile maps' form of that: id -> (id % 8) * (nwg / 8) + id / 8 hands every XCD one contiguous run of positions; the
+// ragged tail (ids beyond the last whole group of 8) keeps the identity map.
+__device__ __forceinline__ int ssg_xcd_remap(int bid) {
+  const int per = (int)gridDim.x >> 3;
+  if (bid < per * 8) bid = (bid & 7) * per + (bid >> 3);
+  return bid;
+}
+// Tap list of a conv / wgrad launch (the `tap_bits` kernel argument): 6 bits per tap, tap t at bit 6 * t, (dy + 2) | (dx + 2) << 3 --
+// offsets -2 .. 5 (validated by the entry points), up to SSG_MAX_TAPS taps in the 64 bits.
+// ssg_tap_dy / ssg_tap_dx: tap t's offset, added to y0 / x0.
+__host__ __device__ __forceinline__ int ssg_tap_field(unsigned long long tap_bits, int t) { return (int)((tap_bits >> (6 * t)) & 63ull); }
+__host__ __device__ __forceinline__ int ssg_tap_dy(unsigned long long tap_bits, int t, int y0 = 0) { return y0 + (ssg_tap_field(tap_bits, t) & 7) - 2; }
+__host__ __device__ __forceinline__ int ssg_tap_dx(unsigned long long tap_bits, int t, int x0 = 0) { return x0 + (ssg_tap_field(tap_bits, t) >> 3) - 2; }
+static inline unsigned long long ssg_pack_taps(const int* dy, const int* dx, int ntaps) {
+  unsigned long long bits = 0;
+  for (int t = 0; t < ntaps; ++t) bits |= (unsigned long long)(((dy[t] + 2) & 7) | (((dx[t] + 2) & 7) << 3)) << (6 * t);
+  return bits;
+}
 // Whether the launches apply their workgroup -> XCD maps (the xcd_swizzle kernel argument).  SSG_XCD_SWIZZLE=0 is for a device
 // partitioned into one XCD per agent (CPX), where the round-robin deal the maps undo does not happen.  Read once per process.
 static inline int ssg_xcd_swizzle() {

@@ -1,4 +1,4 @@
-// Kernel-argument block shared by the two implicit-GEMM conv kernels (internal).
+// Kernel-argument block of the implicit-GEMM conv kernels, their workgroup -> tile map and launch prologue (internal).
 #pragma once
 #include "common.h"
 
@@ -13,10 +13,10 @@ struct ConvArgs {
   int GH, GW, OH, OW;
   int in_sy, in_sx, out_sy, out_sx, out_oy, out_ox;
   int ntaps;
-  unsigned long long tap_bits;   // 6 bits per tap: (dy+2) | (dx+2)<<3
+  unsigned long long tap_bits;   // ssg_tap_dy / ssg_tap_dx (common.h)
   int act; float slope;
   int tiles_x, tiles_y, nsteps;
-  int ntiles_n, xcd_swizzle;     // conv_igemm_dma.hip: Cout tiles (fastest workgroup index), XCD-contiguous tile map
+  int ntiles_n, xcd_swizzle;     // ssg_conv_tile: Cout tiles (fastest workgroup index), XCD-contiguous tile map
   float* ws; int ksplit;         // conv_igemm_halo.hip: split-K slabs [ksplit][N*GH*GW][pad4(Cout)] (ksplit <= 1: off)
   int parity;                    // ssg_conv_desc.parity_merge
   const float* in_scale; const float* in_shift; int in_act; float in_slope;   // ssg_conv_desc.in_scale (conv_igemm_halo_k32.hip, conv_slow.h)
@@ -24,6 +24,36 @@ struct ConvArgs {
   const float* w32;              // split-operand launches: the fp32 packed weights (ssg_conv_desc.w) beside the split pack in `w` (conv_slow.h)
 };
 
+// Workgroup -> tile map of the 1-D grids (ssg_conv_tile_grid).  The dispatcher deals consecutive workgroup ids round-robin over the
+// 8 XCDs (one L2 each); ssg_xcd_remap hands every XCD one contiguous run of tiles, and the Cout tile is the fastest index, so the
+// workgroups that are resident together on an XCD share their input rows (halo and Cout re-reads hit its L2).
+struct ConvTile { int nt, tx, ty, n; };
+__device__ __forceinline__ ConvTile ssg_conv_tile(const ConvArgs& a) {
+  int bid = blockIdx.x;
+  if (a.xcd_swizzle) bid = ssg_xcd_remap(bid);
+  ConvTile t;
+  const int nyt = a.ntiles_n;
+  t.nt = bid % nyt; bid /= nyt;
+  t.tx = bid % a.tiles_x; bid /= a.tiles_x;
+  t.ty = bid % a.tiles_y;
+  t.n = bid / a.tiles_y;
+  return t;
+}
+
+// Launch prologue of those kernels: the tile-map fields for TH x TW-pixel x BN-channel tiles; returns the grid (`slabs` workgroups per tile).
+static inline dim3 ssg_conv_tile_grid(ConvArgs& a, int TW, int TH, int BN, int slabs = 1) {
+  a.tiles_x = (a.GW + TW - 1) / TW;
+  a.tiles_y = (a.GH + TH - 1) / TH;
+  a.xcd_swizzle = ssg_xcd_swizzle();
+  a.ntiles_n = (a.Cout + BN - 1) / BN;
+  return dim3((unsigned)(a.tiles_x * a.tiles_y * a.N * a.ntiles_n * slabs));
+}
+// Once per process and kernel: allow `bytes` of dynamic LDS (the default limit is 64 KiB); on failure the enclosing launch function returns.
+#define SSG_DYN_LDS_ONCE(kernel, bytes, family)                                                                                       \
+  do {                                                                                                                                \
+    static const hipError_t attr__ = hipFuncSetAttribute((const void*)(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (bytes)); \
+    if (attr__ != hipSuccess) { ssg_set_error(family ": LDS attribute: %s", hipGetErrorString(attr__)); return (int)attr__; }         \
+  } while (0)
 
 // conv_igemm_dma.hip: LDS-DMA pipeline for kmode 0, Cout > 32 (variant 0 = <128,128>, 1 = <256,64>)
 int ssg_conv_igemm_dma_launch(const ConvArgs& a, int variant, hipStream_t st);

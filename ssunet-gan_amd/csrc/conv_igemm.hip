@@ -88,8 +88,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a) {
       c = k - t * Cin;
     }
     const bool tv = t < a.ntaps;
-    const int tb = (int)((a.tap_bits >> (6 * (tv ? t : 0))) & 63ull);
-    const int dy = (tb & 7) - 2, dx = (tb >> 3) - 2;
+    const int dy = ssg_tap_dy(a.tap_bits, tv ? t : 0), dx = ssg_tap_dx(a.tap_bits, tv ? t : 0);
     const float* src; int ld, cc;
     if (c < a.C1) { src = a.in1; ld = a.ld1; cc = c; }
     else          { src = a.in2; ld = a.ld2; cc = c - a.C1; }
@@ -266,9 +265,7 @@ ConvArgs to_args(const ssg_conv_desc* d) {
   a.in_sy = d->in_sy; a.in_sx = d->in_sx; a.out_sy = d->out_sy; a.out_sx = d->out_sx;
   a.out_oy = d->out_oy; a.out_ox = d->out_ox;
   a.ntaps = d->ntaps;
-  a.tap_bits = 0;
-  for (int t = 0; t < d->ntaps; ++t)
-    a.tap_bits |= (unsigned long long)(((d->dy[t] + 2) & 7) | (((d->dx[t] + 2) & 7) << 3)) << (6 * t);
+  a.tap_bits = ssg_pack_taps(d->dy, d->dx, d->ntaps);
   a.act = d->act; a.slope = d->slope;
   a.nsteps = d->Kp / 16;
   a.tiles_x = a.tiles_y = 0;

@@ -43,10 +43,7 @@ __global__ __launch_bounds__(256) void conv_igemm_dma_kernel(const ConvArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
 
-  // Workgroup -> tile map.  The dispatcher deals consecutive workgroup ids round-robin over the 8 XCDs
-  // (one L2 each); id -> (id % 8) * (nwg / 8) + id / 8 hands every XCD one contiguous run of tiles, and
-  // the Cout tile is the fastest index, so the workgroups that are resident together on an XCD share
-  // their input rows (halo and Cout re-reads hit its L2).  The ragged tail keeps the identity map.
+  // the map of ssg_conv_tile (conv_args.h), written out: n0 is formed before the division here
   int bid = blockIdx.x;
   if (a.xcd_swizzle) {
     const int per = (int)gridDim.x >> 3;
@@ -85,8 +82,7 @@ __global__ __launch_bounds__(256) void conv_igemm_dma_kernel(const ConvArgs a) {
     float* st = lds + (s % NSTAGE) * STAGE;
     const int chunk = s / a.ntaps;
     const int t = s - chunk * a.ntaps;
-    const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);
-    const int dy = (tb & 7) - 2, dx = (tb >> 3) - 2;
+    const int dy = ssg_tap_dy(a.tap_bits, t), dx = ssg_tap_dx(a.tap_bits, t);
     const int c0 = chunk * 16;
     const float* src; int ld, cc;
     if (c0 < a.C1) { src = a.in1; ld = a.ld1; cc = c0; } else { src = a.in2; ld = a.ld2; cc = c0 - a.C1; }
@@ -195,18 +191,9 @@ __global__ __launch_bounds__(256) void conv_igemm_dma_kernel(const ConvArgs a) {
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 int launch(const ConvArgs& a0, hipStream_t st) {
   ConvArgs a = a0;
-  constexpr int TH = BM / 16;
-  a.tiles_x = (a.GW + 15) / 16;
-  a.tiles_y = (a.GH + TH - 1) / TH;
-  a.xcd_swizzle = ssg_xcd_swizzle();
-  a.ntiles_n = (a.Cout + BN - 1) / BN;
-  dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N * a.ntiles_n));
+  const dim3 grid = ssg_conv_tile_grid(a, 16, BM / 16, BN);
   constexpr int lds_bytes = NSTAGE * (BM + BN) * 16 * (int)sizeof(float);
-  if (lds_bytes > 64 * 1024) {
-    static const hipError_t attr = hipFuncSetAttribute((const void*)conv_igemm_dma_kernel<BM, BN, WAVES_M, WAVES_N>,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (attr != hipSuccess) { ssg_set_error("conv dma: LDS attribute: %s", hipGetErrorString(attr)); return (int)attr; }
-  }
+  if (lds_bytes > 64 * 1024) SSG_DYN_LDS_ONCE((conv_igemm_dma_kernel<BM, BN, WAVES_M, WAVES_N>), lds_bytes, "conv dma");
   hipLaunchKernelGGL((conv_igemm_dma_kernel<BM, BN, WAVES_M, WAVES_N>), grid, dim3(256), lds_bytes, st, a);
   SSG_LAUNCH_CHECK();
   return SSG_OK;

@@ -33,17 +33,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma_x3_kernel(const ConvArg
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  int bid = blockIdx.x;
-  if (a.xcd_swizzle) {
-    const int per = (int)gridDim.x >> 3;
-    if (bid < per * 8) bid = (bid & 7) * per + (bid >> 3);
-  }
-  const int nyt = a.ntiles_n;
-  const int nt = bid % nyt; bid /= nyt;
-  const int n0 = nt * BN;
-  const int tx = bid % a.tiles_x; bid /= a.tiles_x;
-  const int ty = bid % a.tiles_y;
-  const int n = bid / a.tiles_y;
+  const ConvTile tile = ssg_conv_tile(a);
+  const int nyt = a.ntiles_n, nt = tile.nt, n0 = nt * BN, tx = tile.tx, ty = tile.ty, n = tile.n;
 
   // ---- per-lane DMA source state: piece j of this wave covers tile rows [(wave*A_PC + j)*16, +16)
   const int lr = lane >> 2, lp = lane & 3;
@@ -71,8 +62,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma_x3_kernel(const ConvArg
     unsigned char* st = ldsb + (s % NSTAGE) * STAGE;
     const int chunk = s / a.ntaps;
     const int t = s - chunk * a.ntaps;
-    const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);
-    const int dy = (tb & 7) - 2, dx = (tb >> 3) - 2;
+    const int dy = ssg_tap_dy(a.tap_bits, t), dx = ssg_tap_dx(a.tap_bits, t);
     const int c0 = chunk * 16;
     const bool first = c0 < a.C1;
     const unsigned ldb = (unsigned)(first ? a.ld1 : a.ld2) * 4u;
@@ -153,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma_x3_kernel(const ConvArg
     bool bad = false;
 #pragma unroll
     for (int j = 0; j < NI; ++j) bad |= ssg_nonfinite16(acc[j]);
-    if (__builtin_amdgcn_readfirstlane(__syncthreads_or(bad))) {     // scalar condition: a uniform branch, the accumulators are dead inside it
+    if (ssg_any_nonfinite(bad)) {
       const ConvArgs& as = *ssg_reload_args<ConvArgs>();
 #pragma unroll
       for (int j = 0; j < NI; ++j)
@@ -200,15 +190,10 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma_x3_kernel(const ConvArg
 template <int BN>
 int launch(const ConvArgs& a0, hipStream_t st) {
   ConvArgs a = a0;
-  a.tiles_x = (a.GW + 15) / 16;
-  a.tiles_y = (a.GH + 7) / 8;
-  a.xcd_swizzle = ssg_xcd_swizzle();
-  a.ntiles_n = (a.Cout + BN - 1) / BN;
-  dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N * a.ntiles_n));
+  const dim3 grid = ssg_conv_tile_grid(a, 16, 8, BN);
   constexpr int lds_bytes = NSTAGE * (128 * 64 + BN * XROW) + 1024;
   static_assert(lds_bytes <= 80 * 1024, "two workgroups per CU");
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_igemm_dma_x3_kernel<BN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (attr != hipSuccess) { ssg_set_error("conv dma x3: LDS attribute: %s", hipGetErrorString(attr)); return (int)attr; }
+  SSG_DYN_LDS_ONCE(conv_igemm_dma_x3_kernel<BN>, lds_bytes, "conv dma x3");
   hipLaunchKernelGGL((conv_igemm_dma_x3_kernel<BN>), grid, dim3(256), lds_bytes, st, a);
   SSG_LAUNCH_CHECK();
   return SSG_OK;

@@ -60,6 +60,7 @@ __device__ __forceinline__ void halo_body(const ConvArgs& a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
 
+  // the map of ssg_conv_tile (conv_args.h) with the split-K slab between the Cout tile and tx
   int bid = blockIdx.x;
   if (a.xcd_swizzle) {
     const int per = (int)gridDim.x >> 3;
@@ -170,8 +171,7 @@ __device__ __forceinline__ void halo_body(const ConvArgs& a) {
       if (t < APW) issue_a(chunk + 1, t);
       issue_b(s + 2);
 
-      const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);
-      const int toff = ((tb & 7) - 2) * HW + ((tb >> 3) - 2);          // dy*HW + dx
+      const int toff = ssg_tap_dy(a.tap_bits, t) * HW + ssg_tap_dx(a.tap_bits, t);
       const float* Bb = ldsB + (s % 3) * BSTG + (wn * WTN + l31) * 16;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -254,12 +254,8 @@ int launch(const ConvArgs& a0, hipStream_t st) {
   ConvArgs a = a0;
   constexpr int TW = 1 << TWL, TH = BM / TW;
   constexpr int AP = ((TH + 2) * (TWL == 5 ? TW + 2 : 32) + 15) / 16;
-  a.tiles_x = (a.GW + TW - 1) / TW;
-  a.tiles_y = (a.GH + TH - 1) / TH;
-  a.xcd_swizzle = ssg_xcd_swizzle();
-  a.ntiles_n = (a.Cout + BN - 1) / BN;
   if (a.ksplit < 1) a.ksplit = 1;
-  dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N * a.ntiles_n * a.ksplit));
+  const dim3 grid = ssg_conv_tile_grid(a, TW, TH, BN, a.ksplit);
   constexpr int lds_bytes = (2 * AP * 256 + 3 * BN * 16) * (int)sizeof(float);
   static_assert(lds_bytes <= 64 * 1024, "LDS budget");
   if (a.ksplit > 1) {
@@ -291,8 +287,7 @@ bool ssg_conv_halo_ok(const ConvArgs& a) {
   if (a.ntaps != 9 || a.in_sy != 1 || a.in_sx != 1 || a.kmode != 0) return false;
   unsigned seen = 0;
   for (int t = 0; t < 9; ++t) {
-    const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);
-    const int dy = (tb & 7) - 2, dx = (tb >> 3) - 2;
+    const int dy = ssg_tap_dy(a.tap_bits, t), dx = ssg_tap_dx(a.tap_bits, t);
     if (dy < -1 || dy > 1 || dx < -1 || dx > 1) return false;
     seen |= 1u << ((dy + 1) * 3 + dx + 1);
   }

@@ -98,17 +98,8 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 8) ? 
   const int l15 = lane & 15, kg = lane >> 4;
 
   SSG_STAMP(7);                                            // (probe build) kernel entry; stamp 0 follows the address set-up
-  int bid = blockIdx.x;
-  if (a.xcd_swizzle) {
-    const int per = (int)gridDim.x >> 3;
-    if (bid < per * 8) bid = (bid & 7) * per + (bid >> 3);
-  }
-  const int nyt = a.ntiles_n;
-  const int nt = bid % nyt; bid /= nyt;
-  const int n0 = nt * BN;
-  const int tx = bid % a.tiles_x; bid /= a.tiles_x;
-  const int ty = bid % a.tiles_y;
-  const int n = bid / a.tiles_y;
+  const ConvTile tile = ssg_conv_tile(a);
+  const int nyt = a.ntiles_n, nt = tile.nt, n0 = nt * BN, tx = tile.tx, ty = tile.ty, n = tile.n;
 
   const int nchunks = (a.C1 + a.C2) >> 5;
   const int nsteps = nchunks * 9;
@@ -241,7 +232,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 8) ? 
         if (t == LD_T) load_px(chunk + 1);
       }
 
-      const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);
+      const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);               // ssg_tap_dy / ssg_tap_dx (common.h) written out
       const int toff = (((tb & 7) - 2) * HW + ((tb >> 3) - 2)) * 16;
       const unsigned char* st = ring + (t % 3) * BSTG + wfrag;            // s % 3 == t % 3 (9 steps per chunk)
       bf16x8 p[MI][3], w[NI][3];
@@ -303,13 +294,9 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 8) ? 
       for (int j = 0; j < NI; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) bad |= ssg_nonfinite(acc[i][j][r]);
-    if (__builtin_amdgcn_readfirstlane(__syncthreads_or(bad))) {     // scalar condition: a uniform branch, the accumulators are dead inside it                         // also: every wave has left the main loop, LDS is scratch
+    if (ssg_any_nonfinite(bad)) {
       float* scr = (float*)lds + tid;                    // value e of this thread at scr[e * threads]
-      // the argument block is re-read from the kernarg segment HERE (opaque pointer): kept live in SGPRs across the main loop for
-      // this cold path, its fields spilled 6 registers of the hot loop
-      const ConvArgs* ap = (const ConvArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-      asm volatile("" : "+s"(ap));
-      const ConvArgs& as = *ap;
+      const ConvArgs& as = *ssg_reload_args<ConvArgs>();
       for (int e = 0; e < MI * NI * 4; ++e) {
         const int i = e / (NI * 4), j = (e >> 2) % NI, r = e & 3;
         const int p = wm * WTM + i * 16 + l15;
@@ -469,18 +456,12 @@ int launch(const ConvArgs& a0, hipStream_t st) {
   ConvArgs a = a0;
   constexpr int NW = WAVES_M * WAVES_N;
   constexpr int HR = (TH + 2) * 34, NPIX = (HR + 15) / 16 * 16;
-  a.tiles_x = (a.GW + 31) / 32;
-  a.tiles_y = (a.GH + TH - 1) / TH;
-  a.xcd_swizzle = ssg_xcd_swizzle();
-  a.ntiles_n = (a.Cout + BN - 1) / BN;                    // narrow tiles (BN 16 / 32): the last columns may be padding
-  dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N * a.ntiles_n));
+  const dim3 grid = ssg_conv_tile_grid(a, 32, TH, BN);    // narrow tiles (BN 16 / 32): the last columns may be padding
   constexpr int lds_bytes = (3 * 4 * (NPIX * 16 + 64) + 1023) / 1024 * 1024 + 3 * BN * 192 + 1024;
   static_assert(lds_bytes <= 160 * 1024 && (NW != 4 || BN <= 32 || lds_bytes <= 80 * 1024), "LDS budget");
   constexpr int tab_bytes = XF ? 2 * SSG_K32_XF_MAXC * 4 : 0;       // scale | shift of up to SSG_K32_XF_MAXC input channels
   static_assert(lds_bytes + tab_bytes <= 160 * 1024, "LDS budget with the input-transform table");
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_halo_k32_kernel<TH, BN, WAVES_M, WAVES_N, XF, BWD>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes + tab_bytes);
-  if (attr != hipSuccess) { ssg_set_error("conv halo k32: LDS attribute: %s", hipGetErrorString(attr)); return (int)attr; }
+  SSG_DYN_LDS_ONCE((conv_halo_k32_kernel<TH, BN, WAVES_M, WAVES_N, XF, BWD>), lds_bytes + tab_bytes, "conv halo k32");
   hipLaunchKernelGGL((conv_halo_k32_kernel<TH, BN, WAVES_M, WAVES_N, XF, BWD>), grid, dim3(NW * 64), lds_bytes + (XF ? 2 * a.C1 * 4 : 0), st, a);
   SSG_LAUNCH_CHECK();
   return SSG_OK;

@@ -73,17 +73,8 @@ __global__ __launch_bounds__(256, (BN == 64 && !PARITY) ? 3 : 2) void conv_igemm
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
 
-  int bid = blockIdx.x;
-  if (a.xcd_swizzle) {
-    const int per = (int)gridDim.x >> 3;
-    if (bid < per * 8) bid = (bid & 7) * per + (bid >> 3);
-  }
-  const int nyt = a.ntiles_n;
-  const int nt = bid % nyt; bid /= nyt;
-  const int n0 = nt * BN;
-  const int tx = bid % a.tiles_x; bid /= a.tiles_x;
-  const int ty = bid % a.tiles_y;
-  const int n = bid / a.tiles_y;
+  const ConvTile tile = ssg_conv_tile(a);
+  const int nyt = a.ntiles_n, nt = tile.nt, n0 = nt * BN, tx = tile.tx, ty = tile.ty, n = tile.n;
 
   // ---- DMA sources through buffer descriptors (`buffer_load_dwordx4 ... offen lds`): the per-piece part of an address is a
   // SCALAR offset and a lane whose halo pixel lies outside the image carries a byte offset beyond the range, which the
@@ -209,8 +200,7 @@ __global__ __launch_bounds__(256, (BN == 64 && !PARITY) ? 3 : 2) void conv_igemm
       if (t < APW) issue_a(chunk + 1, t);
       issue_b(s + 2);
 
-      const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);
-      const int toff = ((tb & 7) - 2) * HW + ((tb >> 3) - 2);
+      const int toff = ssg_tap_dy(a.tap_bits, t) * HW + ssg_tap_dx(a.tap_bits, t);
       const unsigned char* Bst = ldsB + (t % 3) * BSTG;
       bf16x8 a1[MI], a2[MI], a3[MI], b1[NI], b2[NI], b3[NI];
 #pragma unroll
@@ -257,7 +247,7 @@ __global__ __launch_bounds__(256, (BN == 64 && !PARITY) ? 3 : 2) void conv_igemm
       for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < NI; ++j) bad |= ssg_nonfinite16(acc[q][i][j]);
-    if (__builtin_amdgcn_readfirstlane(__syncthreads_or(bad))) {
+    if (ssg_any_nonfinite(bad)) {
       const ConvArgs& as = *ssg_reload_args<ConvArgs>();
       if constexpr (PARITY) {
         // 128 accumulators per lane: the slow path writes the four classes itself (the merged launch has no bias, residual or
@@ -336,15 +326,10 @@ int launch(const ConvArgs& a0, hipStream_t st) {
   ConvArgs a = a0;
   constexpr int TW = 32, TH = 4;
   constexpr int AP = ((TH + 2) * (TW + 2) + 15) / 16;
-  a.tiles_x = (a.GW + TW - 1) / TW;
-  a.tiles_y = (a.GH + TH - 1) / TH;
-  a.xcd_swizzle = ssg_xcd_swizzle();
-  a.ntiles_n = (a.Cout + BN - 1) / BN;
-  dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N * a.ntiles_n));
+  const dim3 grid = ssg_conv_tile_grid(a, TW, TH, BN);
   constexpr int lds_bytes = AP * 1024 + ((AP * 16 * XROW + 1023) / 1024) * 1024 + 3 * BN * XROW + 1024;
   static_assert(lds_bytes <= 80 * 1024, "two workgroups per CU");
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_igemm_halo_x3_kernel<128, BN, WAVES_M, WAVES_N, PARITY>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (attr != hipSuccess) { ssg_set_error("conv halo x3: LDS attribute: %s", hipGetErrorString(attr)); return (int)attr; }
+  SSG_DYN_LDS_ONCE((conv_igemm_halo_x3_kernel<128, BN, WAVES_M, WAVES_N, PARITY>), lds_bytes, "conv halo x3");
   hipLaunchKernelGGL((conv_igemm_halo_x3_kernel<128, BN, WAVES_M, WAVES_N, PARITY>), grid, dim3(256), lds_bytes, st, a);
   SSG_LAUNCH_CHECK();
   return SSG_OK;
@@ -384,8 +369,7 @@ bool ssg_conv_halo_x3_parity_ok(const ConvArgs& a) {
   if (a.GH != (a.OH + 1) / 2 || a.GW != (a.OW + 1) / 2 || a.Cout % 64 || a.bias || a.res || a.bnpart) return false;
   static const int want[9][2] = {{0, 0}, {0, 1}, {0, 0}, {1, 0}, {0, 0}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};   // (dy, dx) per tap
   for (int t = 0; t < 9; ++t) {
-    const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);
-    if ((tb & 7) - 2 != want[t][0] || (tb >> 3) - 2 != want[t][1]) return false;
+    if (ssg_tap_dy(a.tap_bits, t) != want[t][0] || ssg_tap_dx(a.tap_bits, t) != want[t][1]) return false;
   }
   const unsigned long long bytes = (unsigned long long)a.N * a.H * a.W * (unsigned long long)(a.ld1 > a.ld2 ? a.ld1 : a.ld2) * 4ull;
   return bytes <= 0xfffffff0ull && a.W >= 17;               // 32-bit buffer offsets; 32-wide tiles

@@ -26,8 +26,7 @@ __device__ inline float ssg_conv_slow_value(const ConvArgs& a, int n, int gy, in
   const int Cin = a.C1 + a.C2;
   float acc = 0.f;
   for (int t = t_lo; t < t_hi; ++t) {
-    const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);
-    const int iy = gy * a.in_sy + (tb & 7) - 2, ix = gx * a.in_sx + (tb >> 3) - 2;
+    const int iy = ssg_tap_dy(a.tap_bits, t, gy * a.in_sy), ix = ssg_tap_dx(a.tap_bits, t, gx * a.in_sx);
     // a tap outside the image multiplies ZEROS, it is not skipped: 0 * inf = NaN is what the zero padding of the fp32 kernels (and
     // of F.conv2d) produces under a non-finite weight
     const bool inside = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
@@ -66,6 +65,12 @@ __device__ __forceinline__ bool ssg_nonfinite16(const f32x16& v) {
   return bad;
 }
 
+// The detect-and-branch step after a main loop: every thread ORs ssg_nonfinite over its accumulators into `bad`, then
+//   if (ssg_any_nonfinite(bad)) { const Args& as = *ssg_reload_args<Args>(); ...recompute... }
+// The vote is also a barrier (every wave has left the main loop: LDS is scratch), and its result is a SCALAR condition: a uniform
+// branch, the accumulators are dead inside it.
+__device__ __forceinline__ bool ssg_any_nonfinite(bool bad) { return __builtin_amdgcn_readfirstlane(__syncthreads_or(bad)); }
+
 // the kernel's argument block, re-read from the kernarg segment at the point of use: its fields must not stay live in SGPRs across
 // the hot loop for the sake of this cold path (that spilled registers of the k32 kernel)
 template <class Args>
@@ -98,8 +103,7 @@ __device__ __forceinline__ float ssg_wgrad_slow_pixel(const WgArgs& a, int dyt, 
 // pixels P0 <= P < P1 of the flat N x GH x GW grid (wgrad_dma_x3_kernel's slabs)
 __device__ inline float ssg_wgrad_slow_value_flat(const WgArgs& a, int t, int c, int co, long long P0, long long P1) {
   if (co >= a.Cout || c >= a.C1 + a.C2 || t >= a.ntaps) return 0.f;
-  const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);
-  const int dyt = (tb & 7) - 2, dxt = (tb >> 3) - 2;
+  const int dyt = ssg_tap_dy(a.tap_bits, t), dxt = ssg_tap_dx(a.tap_bits, t);
   const long long GHW = (long long)a.GH * a.GW;
   int n = (int)(P0 / GHW); const int rem = (int)(P0 - n * GHW);
   int gy = rem / a.GW, gx = rem - gy * a.GW;
@@ -116,8 +120,7 @@ __device__ inline float ssg_wgrad_slow_value_flat(const WgArgs& a, int t, int c,
 template <bool XF = false>
 __device__ inline float ssg_wgrad_slow_value_strips(const WgArgs& a, int t, int c, int co, long long S0, long long S1, int KPX) {
   if (co >= a.Cout || c >= a.C1 + a.C2 || t >= a.ntaps) return 0.f;
-  const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);
-  const int dyt = (tb & 7) - 2, dxt = (tb >> 3) - 2;
+  const int dyt = ssg_tap_dy(a.tap_bits, t), dxt = ssg_tap_dx(a.tap_bits, t);
   const int XB = (a.GW + KPX - 1) / KPX;
   float acc = 0.f;
   for (long long S = S0; S < S1; ++S) {

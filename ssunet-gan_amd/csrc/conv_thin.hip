@@ -50,8 +50,7 @@ __global__ __launch_bounds__(256) void thin_small_cout_kernel(const ThinArgs a) 
       const int c = cc + 4 * l16;
       if (c < a.C && pok) {
         for (int t = 0; t < a.ntaps; ++t) {
-          const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);
-          const int iy = y + (tb & 7) - 2, ix = x + (tb >> 3) - 2;
+          const int iy = ssg_tap_dy(a.tap_bits, t, y), ix = ssg_tap_dx(a.tap_bits, t, x);
           if ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W) {
             const f32x4 v = *(const f32x4*)(a.in + ((size_t)(n * a.H + iy) * a.W + ix) * a.ld + c);
             const float* wp = wl + (size_t)t * CO * a.C + c;
@@ -100,9 +99,7 @@ ThinArgs make_args(const ssg_conv_desc* d) {
   a.in = d->in1; a.w = d->w; a.bias = d->bias; a.res = d->res; a.out = d->out;
   a.C = d->C1; a.ld = d->ld1; a.N = d->N; a.H = d->H; a.W = d->W; a.Kp = d->Kp; a.kmode = d->kmode;
   a.ldr = d->ldr; a.Cout = d->Cout; a.ldo = d->ldo; a.ntaps = d->ntaps;
-  a.tap_bits = 0;
-  for (int t = 0; t < d->ntaps; ++t)
-    a.tap_bits |= (unsigned long long)(((d->dy[t] + 2) & 7) | (((d->dx[t] + 2) & 7) << 3)) << (6 * t);
+  a.tap_bits = ssg_pack_taps(d->dy, d->dx, d->ntaps);
   a.act = d->act; a.slope = d->slope;
   return a;
 }

@@ -42,8 +42,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgArgs a) {
   const bool arow_ok = arow < a.M;
   int at = 0, ac = 0;
   if (arow_ok) { at = arow / Cin; ac = arow - at * Cin; }
-  const int tb = (int)((a.tap_bits >> (6 * at)) & 63ull);
-  const int ady = (tb & 7) - 2, adx = (tb >> 3) - 2;
+  const int ady = ssg_tap_dy(a.tap_bits, at), adx = ssg_tap_dx(a.tap_bits, at);
   const float* asrc; int ald, acc_;
   if (ac < a.C1) { asrc = a.in1; ald = a.ld1; acc_ = ac; } else { asrc = a.in2; ald = a.ld2; acc_ = ac - a.C1; }
   // B: column quad
@@ -337,9 +336,7 @@ extern "C" int ssg_conv2d_wgrad_f32(const ssg_wgrad_desc* d, void* stream) {
   a.C1 = d->C1; a.C2 = d->C2; a.ld1 = d->ld1; a.ld2 = d->C2 ? d->ld2 : d->ld1;
   a.N = d->N; a.H = d->H; a.W = d->W; a.Cout = d->Cout; a.ldd = d->ldd; a.GH = d->GH; a.GW = d->GW;
   a.in_sy = d->in_sy; a.in_sx = d->in_sx; a.ntaps = d->ntaps;
-  a.tap_bits = 0;
-  for (int t = 0; t < d->ntaps; ++t)
-    a.tap_bits |= (unsigned long long)(((d->dy[t] + 2) & 7) | (((d->dx[t] + 2) & 7) << 3)) << (6 * t);
+  a.tap_bits = ssg_pack_taps(d->dy, d->dx, d->ntaps);
   a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.in_act = d->in_act; a.in_slope = d->in_slope;
   a.M = d->ntaps * (d->C1 + d->C2);
   a.Ptot = (long long)d->N * d->GH * d->GW;

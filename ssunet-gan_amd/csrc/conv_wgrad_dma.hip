@@ -76,8 +76,7 @@ __device__ __forceinline__ void wgrad_dma_body(const WgArgs& a) {
     a_rowok[j] = row < a.M;
     int t = 0, c = 0;
     if (a_rowok[j]) { t = row / Cin; c = row - t * Cin; }
-    const int tb = (int)((a.tap_bits >> (6 * t)) & 63ull);
-    a_dy[j] = (tb & 7) - 2; a_dx[j] = (tb >> 3) - 2;
+    a_dy[j] = ssg_tap_dy(a.tap_bits, t); a_dx[j] = ssg_tap_dx(a.tap_bits, t);
     if (c < a.C1) { a_base[j] = a.in1 + c; a_ld[j] = a.ld1; } else { a_base[j] = a.in2 + (c - a.C1); a_ld[j] = a.ld2; }
     const long long P = step0 * BKP + px;
     a_n[j] = (int)(P / GHW); const int rem = (int)(P - (long long)a_n[j] * GHW);
@@ -186,7 +185,7 @@ __device__ __forceinline__ void wgrad_dma_body(const WgArgs& a) {
     for (int i = 0; i < MI; ++i)
 #pragma unroll
       for (int j = 0; j < NI; ++j) bad |= ssg_nonfinite16(acc[i][j]);
-    if (__builtin_amdgcn_readfirstlane(__syncthreads_or(bad))) {     // scalar condition: a uniform branch, the accumulators are dead inside it
+    if (ssg_any_nonfinite(bad)) {
       const WgArgs& as = *ssg_reload_args<WgArgs>();
       const long long P0 = step0 * BKP, P1e = (step0 + nsteps) * BKP;
       const long long P1 = P1e < as.Ptot ? P1e : as.Ptot;

@@ -311,7 +311,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_x3_kernel(const WgArgs a) {
     bool bad = false;
 #pragma unroll
     for (int t = 0; t < 9; ++t) bad |= ssg_nonfinite16(acc[t]);
-    if (__builtin_amdgcn_readfirstlane(__syncthreads_or(bad))) {
+    if (ssg_any_nonfinite(bad)) {
       // the slab values are written by the slow path itself (144 accumulators per lane: refilling them would spill)
       const WgArgs& as = *ssg_reload_args<WgArgs>();
 #pragma unroll 1

@@ -241,7 +241,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_k32_kernel(const WgArgs a) {
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) bad |= ssg_nonfinite(tot[t][j][r]);
-    if (__builtin_amdgcn_readfirstlane(__syncthreads_or(bad))) {     // scalar condition: a uniform branch, the accumulators are dead inside it
+    if (ssg_any_nonfinite(bad)) {
       const WgArgs& as = *ssg_reload_args<WgArgs>();
 #pragma unroll
       for (int t = 0; t < 9; ++t)
@@ -292,9 +292,8 @@ long long ssg_wgrad_k32_steps(const ssg_wgrad_desc* d) { return (long long)d->N 
 
 int ssg_wgrad_k32_launch(const WgArgs& a, dim3 grid, hipStream_t st) {
   constexpr int lds_bytes = XIMG + DIMG;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)wgrad_k32_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  static const hipError_t attr_xf = hipFuncSetAttribute((const void*)wgrad_k32_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes + 512);
-  if (attr != hipSuccess || attr_xf != hipSuccess) { ssg_set_error("wgrad k32: LDS attribute: %s", hipGetErrorString(attr != hipSuccess ? attr : attr_xf)); return (int)(attr != hipSuccess ? attr : attr_xf); }
+  SSG_DYN_LDS_ONCE(wgrad_k32_kernel<false>, lds_bytes, "wgrad k32");
+  SSG_DYN_LDS_ONCE(wgrad_k32_kernel<true>, lds_bytes + 512, "wgrad k32");
   if (a.in_scale) hipLaunchKernelGGL(wgrad_k32_kernel<true>, grid, dim3(512), lds_bytes + 512, st, a);
   else hipLaunchKernelGGL(wgrad_k32_kernel<false>, grid, dim3(512), lds_bytes, st, a);
   SSG_LAUNCH_CHECK();

@@ -50,11 +50,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const GemmArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;             // wm: channel half (A operand), wn: pixel half (B operand)
 
-  int bid = blockIdx.x;
-  {
-    const int per = (int)gridDim.x >> 3;                // XCD-contiguous tile runs (bijective on the full part)
-    if (bid < per * 8) bid = (bid & 7) * per + (bid >> 3);
-  }
+  const int bid = ssg_xcd_remap(blockIdx.x);               // XCD-contiguous tile runs (bijective on the full part)
   const int n0 = (bid % a.ntiles_n) * GB_N;
   const long long p0 = (long long)(bid / a.ntiles_n) * GB_M;
 
