@@ -447,7 +447,8 @@ int64_t ssg_dwconv2d_wgrad_workspace_bytes(int N, int OH, int OW, int C, int KH,
 int ssg_dwconv2d_wgrad_f32(const float* in, int N, int H, int W, int C, int ld, const float* dout, int lddo, int KH, int KW,
                            int stride, int pad_top, int pad_left, int OH, int OW, float* dw, void* ws, void* stream);
 /* element-wise: swish x*sigmoid(x) with the reference's backward (efficientnet_pytorch/utils.py:37-48),
- * sigmoid (SE gate, model.py:79), Gaussian exp(-x^2) (xresidualblock.py:5-7) */
+ * sigmoid (SE gate, model.py:79), Gaussian exp(-x^2) (xresidualblock.py:5-7).  The forward takes the REAL channel count C (any
+ * C > 0, pixel strides multiples of 4) and writes the pad lanes [C, pad4(C)) as 0: sigmoid(0) and exp(-0) are not. */
 #define SSG_UNARY_SWISH 0
 #define SSG_UNARY_SIGMOID 1
 #define SSG_UNARY_GAUSSIAN 2

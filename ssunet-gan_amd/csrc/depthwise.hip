@@ -372,8 +372,9 @@ void launch_dw_wgrad_s1(const DwArgs<T>& a, long long parts, long long rpp, doub
 // ---------------------------------------------------------------- unary ops (fwd / bwd)
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
+// C = real channels: sigmoid(0) and exp(-0) are not 0, so the pad lanes [C, pad4(C)) of the last quad are written as 0 here
 __global__ __launch_bounds__(256) void unary_fwd_kernel(const float* __restrict__ x, int ldx, long long P, int C, int op, float* __restrict__ y, int ldy) {
-  const int CQ = C / 4;
+  const int CQ = (C + 3) / 4;
   GRID_STRIDE(i, P * CQ) {
     const long long p = i / CQ; const int cq = (int)(i - p * CQ);
     const f32x4 v = *(const f32x4*)(x + p * ldx + 4 * cq);
@@ -381,7 +382,8 @@ __global__ __launch_bounds__(256) void unary_fwd_kernel(const float* __restrict_
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float z = v[e];
-      o[e] = op == SSG_UNARY_SWISH ? z * sigm(z) : (op == SSG_UNARY_SIGMOID ? sigm(z) : expf(-(z * z)));
+      const float r = op == SSG_UNARY_SWISH ? z * sigm(z) : (op == SSG_UNARY_SIGMOID ? sigm(z) : expf(-(z * z)));
+      o[e] = 4 * cq + e < C ? r : 0.f;
     }
     *(f32x4*)(y + p * ldy + 4 * cq) = o;
   }
@@ -623,8 +625,8 @@ extern "C" int ssg_dwconv2d_wgrad_bf16(const void* in, int N, int H, int W, int 
 }
 
 extern "C" int ssg_unary_fwd_f32(const float* x, int ldx, int64_t P, int C, int op, float* y, int ldy, void* stream) {
-  SSG_REQUIRE(x && y && P > 0 && C > 0 && C % 4 == 0 && op >= 0 && op <= 2, SSG_EINVAL, "unary_fwd: bad args");
-  hipLaunchKernelGGL(unary_fwd_kernel, dim3(elem_grid(P * (C / 4))), dim3(256), 0, (hipStream_t)stream, x, ldx, (long long)P, C, op, y, ldy);
+  SSG_REQUIRE(x && y && P > 0 && C > 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= C && ldy >= C && op >= 0 && op <= 2, SSG_EINVAL, "unary_fwd: bad args");
+  hipLaunchKernelGGL(unary_fwd_kernel, dim3(elem_grid(P * ((C + 3) / 4))), dim3(256), 0, (hipStream_t)stream, x, ldx, (long long)P, C, op, y, ldy);
   SSG_LAUNCH_CHECK();
   return SSG_OK;
 }

@@ -75,6 +75,8 @@ __global__ void linear_finish_kernel(const float* __restrict__ part, int ksplit,
   if (act == SSG_ACT_RELU) v = v < 0.f ? 0.f : v;
   else if (act == SSG_ACT_LRELU) v = v > 0.f ? v : v * slope;
   y[(size_t)(n0 + s) * ldy + c] = v;
+  if (c == o - 1)                                  // the row's pad lanes [o, pad4(o)) stay zero (NHWC-with-stride contract)
+    for (int z = o; z < ((o + 3) & ~3) && z < ldy; ++z) y[(size_t)(n0 + s) * ldy + z] = 0.f;
 }
 
 // Weight gradient of a linear layer, dw[o][k] = sum_n dy[n][o] * x[n][k] (models_seg_gan.py:281-283: fc1 is 18 432 -> 1024,

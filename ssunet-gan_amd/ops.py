@@ -462,7 +462,9 @@ def _conv_dgrad_impl(dy, weight, stride, pad, h, w, c_lo, c_hi, res=None, wscale
         except _Declined:
             pass
     if any(len(t) == 0 for _, _, t in classes):
-        dx.zero_()
+        # no launch writes the pixels of a class without taps: fill the whole buffer, pad lanes included (dx.zero_() on the
+        # logical view left lane 3 of a 3-channel gradient unwritten)
+        _relabel(dx, _ld(dx)).zero_()
     for py, px, taps in classes:
         gh, gw = (h - py + s - 1) // s, (w - px + s - 1) // s
         if not taps or gh <= 0 or gw <= 0:
@@ -1209,6 +1211,8 @@ class _NanToZero(torch.autograd.Function):
         ld = nhwc_ld(x) if x.dim() == 4 else None
         if ld is not None:                          # operate on the whole padded buffer
             n, c, h, w = x.shape
+            if ld != pad4(c):                       # a channel slice of a wider buffer: the other lanes are somebody else's
+                raise ValueError('nan_to_zero_: pixel stride %d is wider than the %d channels (channel slice of another tensor)' % (ld, c))
             dense = x.as_strided((n * h * w * ld,), (1,))
         elif x.is_contiguous():
             dense = x.view(-1)
@@ -1228,8 +1232,12 @@ class _NanToZero(torch.autograd.Function):
         if ctx.nhwc:
             g = to_nhwc(g)
             n, c, h, w = g.shape
-            ld = _ld(g)
-            out = new_nhwc(n, c, h, w, g.device, ld=ld)
+            ld = pad4(c)                            # the mask follows x's rows, and x was compact (forward)
+            if _ld(g) != ld:                        # a channel slice of a wider gradient (concat / add hand such views up): its
+                gc = new_nhwc(n, c, h, w, g.device)             # own lanes into compact rows first (c % 4 == 0 here, see nhwc_ld)
+                call('ssg_copy_channels_f32', ptr(g), _ld(g), n * h * w, c, ptr(gc), ld, stream_ptr())
+                g = gc
+            out = new_nhwc(n, c, h, w, g.device)
             call('ssg_mask_zero_f32', ptr(g), ptr(mask), n * h * w * ld, ptr(out), stream_ptr())
             return out
         g = g.contiguous()
@@ -1299,7 +1307,7 @@ class _Unary(torch.autograd.Function):
         x = to_nhwc(x)
         n, c, h, w = x.shape
         y = new_nhwc(n, c, h, w, x.device)
-        call('ssg_unary_fwd_f32', ptr(x), _ld(x), n * h * w, pad4(c), op, ptr(y), _ld(y), stream_ptr())
+        call('ssg_unary_fwd_f32', ptr(x), _ld(x), n * h * w, c, op, ptr(y), _ld(y), stream_ptr())
         ctx.save_for_backward(x)
         ctx.op = op
         return y
@@ -1408,6 +1416,8 @@ class _GlobalAvgPool(torch.autograd.Function):
     def backward(ctx, dy):
         n, c, h, w = ctx.cfg
         dy = to_nhwc(dy)
+        if _ld(dy) != c:                            # the kernel reads the pooled gradient as dense [N][C] rows
+            raise ValueError('global_avgpool: gradient rows are %d floats apart, %d expected' % (_ld(dy), c))
         dx = new_nhwc(n, c, h, w, dy.device)
         call('ssg_broadcast_rows_f32', ptr(dy), n, h * w, c, 1.0 / (h * w), ptr(dx), _ld(dx), stream_ptr())
         return dx
@@ -1477,6 +1487,8 @@ class _ChannelScale(torch.autograd.Function):
         n, c, h, w = x.shape
         if tuple(s.shape) != (n, c, 1, 1) or c % 4:
             raise ValueError('channel_scale: gate %s does not match %s' % (tuple(s.shape), tuple(x.shape)))
+        if _ld(s) != c:                             # the kernels read the gate as dense [N][C] rows
+            raise ValueError('channel_scale: gate rows are %d floats apart, %d expected' % (_ld(s), c))
         y = new_nhwc(n, c, h, w, x.device)
         call('ssg_channel_scale_fwd_f32', ptr(x), _ld(x), ptr(s), n, h * w, c, ptr(y), _ld(y), stream_ptr())
         ctx.save_for_backward(x, s)
@@ -1595,6 +1607,8 @@ class _Add(torch.autograd.Function):
         n, c, h, w = a.shape
         if _ld(a) != _ld(b) or a.shape != b.shape:
             raise ValueError('add: shape/stride mismatch')
+        if _ld(a) != pad4(c):                       # whole pixel rows are added: a channel slice would read its neighbours' lanes
+            raise ValueError('add: pixel stride %d is wider than the %d channels (channel slice of another tensor)' % (_ld(a), c))
         y = new_nhwc(n, c, h, w, a.device, ld=_ld(a))
         call('ssg_add_f32', ptr(a), ptr(b), n * h * w * _ld(a), ptr(y), stream_ptr())
         return y
