@@ -160,8 +160,11 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restri
         const float pv = sigmoidf_(xv);
         // d(1 - mean_n dice_n)/dp = -(1/N) * (2 t U - (2I + s)) / U^2
         const float ddice = -(2.f * tv * invU - ratio) / (float)N;
-        g = gs * (k_bce * (pv - tv) + k_dice * ddice * pv * (1.f - pv)) + gm * k_mse * (xv - tv);
-        if (gb != 0.f) g += gb * (pv - tv);
+        // StableBCELoss (losses.py:130-136) is differentiated by autograd term by term: sigmoid(x) - t everywhere but at a
+        // logit of exactly 0, where clamp(min=0) passes the gradient (x >= 0) and |x| has slope 0, which leaves 1 - t
+        const float db = (xv == 0.f ? 1.f : pv) - tv;
+        g = gs * (k_bce * db + k_dice * ddice * pv * (1.f - pv)) + gm * k_mse * (xv - tv);
+        if (gb != 0.f) g += gb * db;
       }
       dp[c] = g;
     }

@@ -65,15 +65,20 @@ __global__ __launch_bounds__(256) void clamp_kernel(float* __restrict__ x, long 
 // param += -(lr/bc1) * m/denom.
 constexpr int ADAM_CHUNK = 4096;
 
+// The kernel has three inlined copies of this function (float4 body, its n & 3 tail, the unaligned scalar loop) and every
+// copy must give the same bits for the same element.  Left to the compiler's contraction each copy fused other products
+// into FMAs, so the roundings are spelled out: FMAs where written (weight decay, v, the parameter), nothing else fused.
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float clip, float lr_bc1, float omb1, float b2,
                                           float omb2, float eps, float wd, float bc2s) {
+#pragma clang fp contract(off)
   if (clip > 0.f) { g = g < -clip ? -clip : g; g = g > clip ? clip : g; }
-  if (wd != 0.f) g = g + wd * p;
-  m = m + (g - m) * omb1;
-  v = v * b2;
-  v = v + (omb2 * g) * g;
+  if (wd != 0.f) g = __builtin_fmaf(wd, p, g);
+  const float dm = (g - m) * omb1;
+  m = m + dm;
+  const float gg = (omb2 * g) * g;
+  v = __builtin_fmaf(v, b2, gg);
   const float denom = sqrtf(v) / bc2s + eps;
-  p = p - lr_bc1 * (m / denom);
+  p = __builtin_fmaf(-lr_bc1, m / denom, p);
 }
 
 __global__ __launch_bounds__(256) void clamp_adam_kernel(const void* const* __restrict__ ptrs, const long long* __restrict__ sizes,

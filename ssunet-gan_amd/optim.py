@@ -26,24 +26,44 @@ def _supported(opt):
     return True
 
 
-def _plan(params, states, device):
-    key = tuple((p.data_ptr(), p.grad.data_ptr(), s['exp_avg'].data_ptr(), s['exp_avg_sq'].data_ptr()) for p, s in zip(params, states))
+def _build_plan(ptrs, sizes, device):
+    """Device-side launch plan of the multi-tensor kernels: 4 pointers and one size per tensor, one block per 4096-element chunk."""
+    blk_t, blk_c = [], []
+    for t, n in enumerate(sizes):
+        for c in range((n + ADAM_CHUNK - 1) // ADAM_CHUNK):
+            blk_t.append(t); blk_c.append(c)
+    return (torch.tensor(ptrs, dtype=torch.int64).to(device), torch.tensor(sizes, dtype=torch.int64).to(device),
+            torch.tensor(blk_t, dtype=torch.int32).to(device), torch.tensor(blk_c, dtype=torch.int32).to(device), len(blk_t))
+
+
+def _cached_plan(key, ptrs, sizes, device):
+    """The plan under `key`.  The cache holds no reference to the tensors and the allocator may hand their addresses to
+    tensors of another size, so every key carries every numel next to the pointers: a plan is only reused for the launch
+    it was built for."""
     hit = _PLAN_CACHE.get(key)
     if hit is not None:
         return hit
-    ptrs, sizes, blk_t, blk_c = [], [], [], []
-    for t, (p, s) in enumerate(zip(params, states)):
-        ptrs += [p.data_ptr(), p.grad.data_ptr(), s['exp_avg'].data_ptr(), s['exp_avg_sq'].data_ptr()]
-        n = p.numel()
-        sizes.append(n)
-        for c in range((n + ADAM_CHUNK - 1) // ADAM_CHUNK):
-            blk_t.append(t); blk_c.append(c)
-    plan = (torch.tensor(ptrs, dtype=torch.int64).to(device), torch.tensor(sizes, dtype=torch.int64).to(device),
-            torch.tensor(blk_t, dtype=torch.int32).to(device), torch.tensor(blk_c, dtype=torch.int32).to(device), len(blk_t))
+    plan = _build_plan(ptrs, sizes, device)
     if len(_PLAN_CACHE) > 64:
         _PLAN_CACHE.clear()
     _PLAN_CACHE[key] = plan
     return plan
+
+
+def _plan(params, states, device):
+    ptrs, sizes = [], []
+    for p, s in zip(params, states):
+        ptrs += [p.data_ptr(), p.grad.data_ptr(), s['exp_avg'].data_ptr(), s['exp_avg_sq'].data_ptr()]
+        sizes.append(p.numel())
+    return _cached_plan((tuple(ptrs), tuple(sizes)), ptrs, sizes, device)
+
+
+def _clamp_plan(params, device):
+    ptrs, sizes = [], []
+    for p in params:
+        ptrs += [p.data_ptr(), 0, 0, 0]
+        sizes.append(p.numel())
+    return _cached_plan(('clampw', tuple(ptrs), tuple(sizes)), ptrs, sizes, device)
 
 
 def clip_adam_step(optimizer, grad_clip=None):
@@ -86,22 +106,10 @@ def clamp_parameters_(params, clip):
     params = [p for p in params]
     if not params:
         return
-    key = ('clampw',) + tuple(p.data_ptr() for p in params)
-    plan = _PLAN_CACHE.get(key)
-    if plan is None:
-        ptrs, sizes, blk_t, blk_c = [], [], [], []
-        for t, p in enumerate(params):
-            _lib.require_gpu(p)
-            if not p.is_contiguous() or p.dtype != torch.float32:
-                raise ValueError('clamp_parameters_: parameters must be contiguous fp32')
-            ptrs += [p.data_ptr(), 0, 0, 0]
-            sizes.append(p.numel())
-            for c in range((p.numel() + ADAM_CHUNK - 1) // ADAM_CHUNK):
-                blk_t.append(t); blk_c.append(c)
-        dev = params[0].device
-        plan = (torch.tensor(ptrs, dtype=torch.int64).to(dev), torch.tensor(sizes, dtype=torch.int64).to(dev),
-                torch.tensor(blk_t, dtype=torch.int32).to(dev), torch.tensor(blk_c, dtype=torch.int32).to(dev), len(blk_t))
-        _PLAN_CACHE[key] = plan
-    ptrs, sizes, blk_t, blk_c, nblk = plan
+    for p in params:
+        _lib.require_gpu(p)
+        if not p.is_contiguous() or p.dtype != torch.float32:
+            raise ValueError('clamp_parameters_: parameters must be contiguous fp32')
+    ptrs, sizes, blk_t, blk_c, nblk = _clamp_plan(params, params[0].device)
     call('ssg_clamp_multi_f32', ptr(ptrs), ptr(sizes), ptr(blk_t), ptr(blk_c), nblk, 0, -float(clip), float(clip), stream_ptr())
     ops.bump_weight_epoch()              # packed-weight caches must see the clamped values

@@ -132,6 +132,75 @@ def test_average_meter_and_optimizer_gate(pkg):
     assert pkg.train_seg_gan.ALPA == 1e-4 and pkg.train_seg_gan.BETA == 1e-3 and pkg.train_seg_gan.GRAD_CLIP == 0.8
 
 
+def _carved(bufs, off, n):
+    """One 'parameter' of n elements at element offset `off` of four shared flat buffers (param, grad, exp_avg, exp_avg_sq)."""
+    p = bufs[0][off:off + n].requires_grad_(True)
+    p.grad = bufs[1][off:off + n]
+    return p, dict(exp_avg=bufs[2][off:off + n], exp_avg_sq=bufs[3][off:off + n])
+
+
+def _check_plan(plan, params, roles):
+    ptrs, sizes, blk_t, blk_c, nblk = plan
+    want_t = [t for t, p in enumerate(params) for _ in range((p.numel() + 4095) // 4096)]
+    want_c = [c for p in params for c in range((p.numel() + 4095) // 4096)]
+    assert sizes.tolist() == [p.numel() for p in params]
+    assert nblk == len(want_t) and blk_t.tolist() == want_t and blk_c.tolist() == want_c
+    assert ptrs.tolist() == [a for r in roles for a in r]
+
+
+def test_launch_plans_follow_sizes_at_recycled_addresses(pkg):
+    """The launch plans of clip_adam_step and clamp_parameters_ are cached by address, and the caching allocator hands the
+    addresses of freed tensors to tensors of another size (a second model or optimizer built after the first was dropped).
+    A plan that hits on pointers alone keeps the old sizes and block list: a 5000-element parameter at the addresses of an
+    earlier 10000-element one would be updated with sizes = [10000] and 3 blocks, 5000 floats past the end of four tensors.
+    Views of shared flat buffers give two 'parameters' identical data_ptr()s for all four roles."""
+    optim = pkg.optim
+    cpu = torch.device('cpu')
+    bufs = [torch.zeros(20000) for _ in range(4)]
+
+    def adam_roles(p, s):
+        return [p.data_ptr(), p.grad.data_ptr(), s['exp_avg'].data_ptr(), s['exp_avg_sq'].data_ptr()]
+
+    def clamp_roles(p):
+        return [p.data_ptr(), 0, 0, 0]
+
+    optim._PLAN_CACHE.clear()
+    # one parameter: 10000 elements, then 5000 at the same four addresses
+    big, sbig = _carved(bufs, 0, 10000)
+    small, ssmall = _carved(bufs, 0, 5000)
+    assert adam_roles(big, sbig) == adam_roles(small, ssmall)
+    _check_plan(optim._plan([big], [sbig], cpu), [big], [adam_roles(big, sbig)])
+    plan = optim._plan([small], [ssmall], cpu)
+    assert plan[1].tolist() == [5000] and plan[4] == 2
+    _check_plan(plan, [small], [adam_roles(small, ssmall)])
+    assert optim._plan([small], [ssmall], cpu) is plan                    # the same launch still hits
+    # two parameters, only the second one's size changes
+    first, sfirst = _carved(bufs, 10000, 3000)
+    for n2 in (7000, 4096):
+        second, ssecond = _carved(bufs, 13000, n2)
+        _check_plan(optim._plan([first, second], [sfirst, ssecond], cpu), [first, second],
+                    [adam_roles(first, sfirst), adam_roles(second, ssecond)])
+    # the weight clamp's plan, same cases
+    _check_plan(optim._clamp_plan([big], cpu), [big], [clamp_roles(big)])
+    plan = optim._clamp_plan([small], cpu)
+    assert plan[1].tolist() == [5000] and plan[4] == 2
+    _check_plan(plan, [small], [clamp_roles(small)])
+    assert optim._clamp_plan([small], cpu) is plan
+    for n2 in (7000, 4096):
+        second, _ = _carved(bufs, 13000, n2)
+        _check_plan(optim._clamp_plan([first, second], cpu), [first, second], [clamp_roles(first), clamp_roles(second)])
+    # an Adam plan and a clamp plan over the same tensors stay apart
+    assert optim._plan([small], [ssmall], cpu) is not optim._clamp_plan([small], cpu)
+    # both kinds are evicted under the one 64-entry cap
+    optim._PLAN_CACHE.clear()
+    for n in range(1, 200):
+        p, s = _carved(bufs, 0, n)
+        optim._clamp_plan([p], cpu)
+        optim._plan([p], [s], cpu)
+        assert len(optim._PLAN_CACHE) <= 65
+    optim._PLAN_CACHE.clear()
+
+
 def test_layout_rules():
     """oracle/ is test infrastructure: nothing in the product package, bench's GPU leg or the header
     may import it; only tests/, __graft_entry__.smoke() and bench.cpu_baseline() do."""
