@@ -424,6 +424,16 @@ int ssg_clamp_adam_multi_f32(const void* const* ptrs, const int64_t* sizes, cons
                              const int32_t* blk_chunk, int nblocks, float clip, double lr, double beta1,
                              double beta2, double eps, double weight_decay, double bias_corr1,
                              double bias_corr2_sqrt, void* stream);
+/* The same clamp fused with the torch.optim.SGD update, the other optimizer the stage-1 config offers
+ * (scripts/train.py:292-294: momentum, nesterov, weight_decay).  Same plan; the record is
+ * {param, grad, momentum_buffer, flags}: flags bit 0 set = first momentum step of this tensor (the
+ * buffer is written with the gradient and not read), momentum_buffer null when momentum == 0.
+ *   g = clamp(grad); grad = g (clip > 0); g += weight_decay * p;
+ *   buf = first ? g : momentum * buf + (1 - dampening) * g; g = nesterov ? g + momentum * buf : buf;
+ *   p -= lr * g */
+int ssg_clamp_sgd_multi_f32(const void* const* ptrs, const int64_t* sizes, const int32_t* blk_tensor,
+                            const int32_t* blk_chunk, int nblocks, float clip, double lr, double momentum,
+                            double dampening, double weight_decay, int nesterov, void* stream);
 int ssg_clamp_f32(float* x, int64_t n, float lo, float hi, void* stream);
 /* clamp member `which` (0 param, 1 grad, 2 exp_avg, 3 exp_avg_sq) of every record of `ptrs` in one
  * launch -- stage 1 clamps the WEIGHTS to +-clip every step (train.py:111-112) */

@@ -1,5 +1,5 @@
 // Element-wise kernels for gfx950 (HBM-bound, 16 B per lane): SPADE modulate fwd/bwd,
-// activation backward, add, NaN masking, clamp, fused clamp+Adam.
+// activation backward, add, NaN masking, clamp, fused clamp+Adam and clamp+SGD.
 // ABI + reference citations: include/ssunet_hip.h.
 #include "common.h"
 
@@ -121,6 +121,60 @@ __global__ __launch_bounds__(256) void clamp_adam_kernel(const void* const* __re
       if (clip > 0.f) { g = g < -clip ? -clip : g; g = g > clip ? clip : g; G[o] = g; }
     }
   }
+}
+
+// ---------------------------------------------------------------- fused clamp + SGD, multi-tensor
+// Same plan as clamp_adam_kernel; the record is {param, grad, momentum_buffer, flags}, flags bit 0 = this tensor's first
+// momentum step (the buffer is written, never read).  Arithmetic order follows torch.optim.SGD's single-tensor path, every
+// add(x, alpha=a) of it as one FMA: weight decay, buf = momentum * buf + (1 - dampening) * g, nesterov, param -= lr * g.
+// `g` comes back clamped.  Like adam_elem, one function for the float4 body, its tail and the unaligned loop, roundings
+// spelled out so that all three give the same bits.
+__device__ __forceinline__ void sgd_elem(float& p, float& g, float& buf, bool first, float clip, float lr, float mom, float omd,
+                                         float wd, bool nesterov) {
+#pragma clang fp contract(off)
+  if (clip > 0.f) { g = g < -clip ? -clip : g; g = g > clip ? clip : g; }
+  float d = g;
+  if (wd != 0.f) d = __builtin_fmaf(wd, p, d);
+  if (mom != 0.f) {
+    buf = first ? d : __builtin_fmaf(omd, d, buf * mom);
+    d = nesterov ? __builtin_fmaf(mom, buf, d) : buf;
+  }
+  p = __builtin_fmaf(-lr, d, p);
+}
+
+__device__ __forceinline__ void sgd_scalar(float* P, float* G, float* B, long long o, bool first, float clip, float lr, float mom,
+                                           float omd, float wd, bool nesterov) {
+  float p = P[o], g = G[o], b = (mom != 0.f && !first) ? B[o] : 0.f;
+  sgd_elem(p, g, b, first, clip, lr, mom, omd, wd, nesterov);
+  P[o] = p;
+  if (mom != 0.f) B[o] = b;
+  if (clip > 0.f) G[o] = g;                      // clip_gradient clamps .grad in place
+}
+
+__global__ __launch_bounds__(256) void clamp_sgd_kernel(const void* const* __restrict__ ptrs, const long long* __restrict__ sizes,
+                                                        const int* __restrict__ blk_tensor, const int* __restrict__ blk_chunk,
+                                                        float clip, float lr, float mom, float omd, float wd, int nesterov) {
+  const int t = blk_tensor[blockIdx.x];
+  const long long base = (long long)blk_chunk[blockIdx.x] * ADAM_CHUNK;
+  float* P = (float*)ptrs[4 * t + 0];
+  float* G = (float*)ptrs[4 * t + 1];
+  float* B = (float*)ptrs[4 * t + 2];            // null when momentum == 0: never dereferenced
+  const bool first = ((uintptr_t)ptrs[4 * t + 3] & 1) != 0;
+  long long n = sizes[t] - base;
+  if (n > ADAM_CHUNK) n = ADAM_CHUNK;
+  const bool vec = ((((uintptr_t)P | (uintptr_t)G | (uintptr_t)B) & 15) == 0);
+  const int nq = vec ? (int)(n / 4) : 0;
+  for (int i = threadIdx.x; i < nq; i += 256) {
+    const long long o = base + 4 * i;
+    f32x4 p = *(f32x4*)(P + o), g = *(f32x4*)(G + o), b = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (mom != 0.f && !first) b = *(f32x4*)(B + o);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { float pe = p[e], ge = g[e], be = b[e]; sgd_elem(pe, ge, be, first, clip, lr, mom, omd, wd, nesterov != 0); p[e] = pe; g[e] = ge; b[e] = be; }
+    *(f32x4*)(P + o) = p;
+    if (mom != 0.f) *(f32x4*)(B + o) = b;
+    if (clip > 0.f) *(f32x4*)(G + o) = g;
+  }
+  for (int i = nq * 4 + threadIdx.x; i < n; i += 256) sgd_scalar(P, G, B, base + i, first, clip, lr, mom, omd, wd, nesterov != 0);
 }
 
 __global__ __launch_bounds__(256) void copy_channels_kernel(const float* __restrict__ src, int lds_, long long P, int C,
@@ -245,6 +299,18 @@ extern "C" int ssg_clamp_adam_multi_f32(const void* const* ptrs, const int64_t* 
   hipLaunchKernelGGL(clamp_adam_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, ptrs, (const long long*)sizes,
                      blk_tensor, blk_chunk, clip, (float)(lr / bias_corr1), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
                      (float)weight_decay, (float)bias_corr2_sqrt);
+  SSG_LAUNCH_CHECK();
+  return SSG_OK;
+}
+
+extern "C" int ssg_clamp_sgd_multi_f32(const void* const* ptrs, const int64_t* sizes, const int32_t* blk_tensor, const int32_t* blk_chunk,
+                                       int nblocks, float clip, double lr, double momentum, double dampening, double weight_decay,
+                                       int nesterov, void* stream) {
+  SSG_REQUIRE(ptrs && sizes && blk_tensor && blk_chunk && nblocks > 0, SSG_EINVAL, "ssg_clamp_sgd_multi_f32: null plan or nblocks <= 0");
+  SSG_REQUIRE(momentum >= 0.0 && (!nesterov || (momentum > 0.0 && dampening == 0.0)), SSG_EINVAL,
+              "ssg_clamp_sgd_multi_f32: nesterov needs momentum > 0 and dampening == 0");
+  hipLaunchKernelGGL(clamp_sgd_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, ptrs, (const long long*)sizes,
+                     blk_tensor, blk_chunk, clip, (float)lr, (float)momentum, (float)(1.0 - dampening), (float)weight_decay, nesterov);
   SSG_LAUNCH_CHECK();
   return SSG_OK;
 }

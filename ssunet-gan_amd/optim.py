@@ -1,9 +1,10 @@
-"""Fused clip + Adam step on a torch.optim.Adam instance (train_seg_gan.py:211-215,229-233).
+"""Fused clip + Adam step on a torch.optim.Adam instance (train_seg_gan.py:211-215,229-233), and the same for the
+torch.optim.SGD that the stage-1 config can ask for instead (train.py:292-294).
 
 The training loop receives stock torch.optim.Adam objects from its caller; this helper runs
 the same update as `clip_gradient(opt, c); opt.step()` in ONE multi-tensor HIP launch while
 keeping the optimizer's own state (`exp_avg`, `exp_avg_sq`, `step`) authoritative, so
-optimizer.state_dict() stays interchangeable with the reference's."""
+optimizer.state_dict() stays interchangeable with the reference's.  clip_sgd_step does the same with SGD's `momentum_buffer`."""
 import math
 
 import torch
@@ -98,6 +99,60 @@ def clip_adam_step(optimizer, grad_clip=None):
         call('ssg_clamp_adam_multi_f32', ptr(ptrs), ptr(sizes), ptr(blk_t), ptr(blk_c), nblk,
              float(grad_clip) if grad_clip else 0.0, float(group['lr']), float(beta1), float(beta2), float(group['eps']),
              float(group['weight_decay']), bc1, bc2_sqrt, stream_ptr())
+    ops.bump_weight_epoch()
+
+
+def _supported_sgd(opt):
+    if type(opt) is not torch.optim.SGD:
+        return False
+    for g in opt.param_groups:
+        if g.get('maximize') or g.get('differentiable'):
+            return False
+        if isinstance(g['lr'], torch.Tensor):
+            return False
+    return True
+
+
+def _sgd_plan(params, bufs, first, device):
+    """Record {param, grad, momentum_buffer or 0, first-step flag}: the flag travels in the pointer array, so it is part of
+    the key.  A tensor's second step has its first step's four addresses and another flag."""
+    ptrs, sizes = [], []
+    for p, b, f in zip(params, bufs, first):
+        ptrs += [p.data_ptr(), p.grad.data_ptr(), b.data_ptr() if b is not None else 0, int(bool(f))]
+        sizes.append(p.numel())
+    return _cached_plan(('sgd', tuple(ptrs), tuple(sizes)), ptrs, sizes, device)
+
+
+def clip_sgd_step(optimizer, grad_clip=None):
+    """Equivalent of `clip_gradient(optimizer, grad_clip); optimizer.step()` for torch.optim.SGD, one launch per group."""
+    if not _supported_sgd(optimizer):
+        raise NotImplementedError('clip_sgd_step supports plain torch.optim.SGD (no maximize/differentiable/tensor lr)')
+    for group in optimizer.param_groups:
+        params = [p for p in group['params'] if p.grad is not None]
+        if not params:
+            continue
+        momentum = float(group['momentum'])
+        bufs, first = [], []
+        for p in params:
+            _lib.require_gpu(p)
+            if not (p.is_contiguous() and p.grad.is_contiguous() and p.dtype == torch.float32 and p.grad.dtype == torch.float32):
+                raise ValueError('clip_sgd_step: parameters and grads must be contiguous fp32')
+            buf = optimizer.state[p].get('momentum_buffer') if momentum != 0 else None
+            first.append(momentum != 0 and buf is None)
+            if first[-1]:                       # torch.optim.SGD clones the gradient here; the kernel writes every element
+                buf = torch.empty_like(p, memory_format=torch.contiguous_format)
+            elif buf is not None and not (buf.is_contiguous() and buf.dtype == torch.float32 and buf.device == p.device
+                                          and buf.numel() == p.numel()):
+                raise ValueError('clip_sgd_step: momentum_buffer must be a contiguous fp32 tensor of the parameter\'s size and device')
+            bufs.append(buf)
+        ptrs, sizes, blk_t, blk_c, nblk = _sgd_plan(params, bufs, first, params[0].device)
+        call('ssg_clamp_sgd_multi_f32', ptr(ptrs), ptr(sizes), ptr(blk_t), ptr(blk_c), nblk,
+             float(grad_clip) if grad_clip else 0.0, float(group['lr']), momentum, float(group['dampening']),
+             float(group['weight_decay']), int(bool(group['nesterov'])), stream_ptr())
+        for p, buf, f in zip(params, bufs, first):
+            if f:
+                optimizer.state[p]['momentum_buffer'] = buf
+    optimizer._opt_called = True             # what lr_scheduler's wrapper of step() records: scheduler.step() does not warn
     ops.bump_weight_epoch()
 
 

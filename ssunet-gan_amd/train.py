@@ -8,7 +8,7 @@ import torch
 
 from . import dp, ops
 from .losses import BCEDiceLoss
-from .optim import clamp_parameters_, clip_adam_step
+from .optim import _supported_sgd, clamp_parameters_, clip_adam_step, clip_sgd_step
 from .utils import AverageMeter
 
 
@@ -54,12 +54,17 @@ def train(epoch, config, train_loader, model, criterion, optimizer, cnn_optimize
             sync.finish()
         if type(optimizer) is torch.optim.Adam:
             clip_adam_step(optimizer, None)                                  # :115 (no gradient clipping in stage 1)
+        elif _supported_sgd(optimizer):
+            clip_sgd_step(optimizer, None)
         else:
             optimizer.step()
             ops.bump_weight_epoch()
         if cnn_optimizer is not None and epoch > 1:                          # :117-119
-            cnn_optimizer.step()
-            ops.bump_weight_epoch()
+            if _supported_sgd(cnn_optimizer):
+                clip_sgd_step(cnn_optimizer, None)
+            else:
+                cnn_optimizer.step()
+                ops.bump_weight_epoch()
         n = input.size(0)
         avg_meters['loss'].update(loss.detach(), n)
         avg_meters['iou'].update(iou.detach(), n)

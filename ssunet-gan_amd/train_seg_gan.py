@@ -5,7 +5,7 @@ What differs from the reference, by design:
   * BCEDice + MSE + IoU + Dice come from ONE fused HIP pass over (logits, target) instead of
     four torch/numpy passes; IoU/Dice stay on the device (the reference syncs twice per step);
   * `clip_gradient` + `optimizer.step()` is one multi-tensor HIP launch that updates the
-    caller's torch.optim.Adam state in place;
+    caller's torch.optim.Adam (or torch.optim.SGD) state in place;
   * with torch.distributed initialised (one process per GPU over RCCL), gradients are
     all-reduced per bucket on a side stream, overlapped with backward (dp.GradSync), which
     replaces nn.DataParallel (train_seg_gan.py:480-481).
@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from . import dp, ops
 from .losses import BCEDiceLoss
-from .optim import clip_adam_step
+from .optim import _supported_sgd, clip_adam_step, clip_sgd_step
 from .srgan_utils import clip_gradient
 from .utils import AverageMeter
 
@@ -40,6 +40,8 @@ def _adv_loss(criterion, logits, label):
 def _step_optimizer(optimizer, grad_clip):
     if type(optimizer) is torch.optim.Adam:
         clip_adam_step(optimizer, grad_clip)
+    elif _supported_sgd(optimizer):
+        clip_sgd_step(optimizer, grad_clip)
     else:                                           # any other optimizer: HIP clamp, then its own step
         if grad_clip is not None:
             clip_gradient(optimizer, grad_clip)
