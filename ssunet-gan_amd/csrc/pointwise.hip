@@ -232,9 +232,13 @@ __global__ __launch_bounds__(256) void pixel_gate_bwd_kernel(const float* __rest
   for (long long it = 0; it < iters; ++it) {
     const long long p = (((long long)blockIdx.x * 256 + threadIdx.x) >> 4) + it * groups;
     const bool ok = p < P;
-    float s = 0.f, acc = 0.f;
+    float s = 0.f, oms = 0.f, acc = 0.f;
     if (ok) {
-      s = 1.f / (1.f + __expf(-g[p * ldg]));
+      const float gv = g[p * ldg], e = __expf(-gv);
+      s = 1.f / (1.f + e);
+      // 1 - s = e * s.  For psi > 0 the subtraction cancels (s -> 1: 1.3e-3 of dg at psi = 10), the product does not; for psi < 0
+      // the subtraction is exact to an ulp and e may overflow (psi < -88: inf * 0), so each side keeps its stable form.
+      oms = gv >= 0.f ? e * s : 1.f - s;
       for (int cq = sub; cq < CQ; cq += 16) {
         const f32x4 xv = *(const f32x4*)(x + p * ldx + 4 * cq), dv = *(const f32x4*)(dy + p * lddy + 4 * cq);
         acc += (dv[0] * xv[0] + dv[1] * xv[1]) + (dv[2] * xv[2] + dv[3] * xv[3]);
@@ -242,7 +246,7 @@ __global__ __launch_bounds__(256) void pixel_gate_bwd_kernel(const float* __rest
       }
     }
     acc += __shfl_xor(acc, 8); acc += __shfl_xor(acc, 4); acc += __shfl_xor(acc, 2); acc += __shfl_xor(acc, 1);
-    if (ok && sub == 0) *(f32x4*)(dg + p * lddg) = f32x4{acc * s * (1.f - s), 0.f, 0.f, 0.f};
+    if (ok && sub == 0) *(f32x4*)(dg + p * lddg) = f32x4{acc * s * oms, 0.f, 0.f, 0.f};
   }
 }
 }  // namespace

@@ -976,6 +976,7 @@ class _MaxPoolSkip(torch.autograd.Function):
         ctx.save_for_backward(idx)
         ctx.hw = (h, w)
         ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)       # an unused output arrives as None in backward, not as a zero tensor to scatter / add
         return y, idx, x
 
     @staticmethod
