@@ -23,6 +23,7 @@ struct T4Args {
   int tapidx[9];             // tap index at window position (dy+1)*3 + (dx+1), or -1
   int act; float slope;
   int groups, waves_per_group, total_units, strips, ybands;
+  int rh;                    // thin-Cout rows form: output rows per workgroup
   int nt_store;              // thin-Cin: non-temporal output stores (output larger than the caches)
   float* gsave; int ldg;     // thin32 SPADE mode: where gamma (+ bias) goes (the backward needs it), pixel stride
 };
@@ -552,7 +553,129 @@ __global__ __launch_bounds__(256) void thin4_cout_kernel(const T4Args a) {
   }
 }
 
-// (A streaming form of this kernel -- a wave walking a column of bands with all 10 rows of a body in a register ring, every row
+// ------------------------------------------------------------------ thin-Cout 3x3 with the taps as MFMA rows
+// The kernel above spends one 4x4x1 MFMA per 4 pixels x 4 channels, loads every input row once per dx and folds 16
+// K-partials per output.  Here the thin side takes the M dimension of a plain fp32 GEMM instead:
+//     P[(window position q, co)][pixel] = sum_c w[co][tap(q)][c] * in[pixel][c]          (M = 9 * Cout rows, K = Cin)
+// on v_mfma_f32_16x16x4_f32 (MT = ceil(9 * Cout / 16) row tiles: 27/32, 36/48, 72/80 useful rows), then
+//     out[y][x][co] = sum_q P[(q, co)][y + q/3 - 1][x + q%3 - 1]                          (q = 0..8, in this order)
+// through an LDS ring of P rows.  A workgroup of four waves marches 64 pixel columns (x0 - 1 .. x0 + 62, 16 per wave) down a
+// band of rows: every input pixel is loaded once (16-byte buffer loads, 64 contiguous bytes per pixel and instruction; the
+// next row is in flight while this one is multiplied), its P column is written once, and the 62 inner columns are summed and
+// stored.  The two halo columns (3 %) and the two halo rows of a band are the only re-reads.  Out-of-image pixels come
+// back as 0 from the descriptor's range check, so their P is 0: the zero padding.  The weights sit in registers in A-operand
+// order (MT * KC * 16 per lane, KC = Cin / 64).  Summation order: channels (in MFMA order) inside a window position, then the
+// positions 0..8, then bias and residual -- fixed, whatever the grid.
+// LDS: P[slot][row][64 columns], column index rotated by 16 * ((row + row / 4) & 3): the accumulator write (rows 4g + r of a
+// tile in lane group g) and the sum's read (rows q * Cout + co, four consecutive co in the four lane groups) both spread
+// over all banks.  RING = 4 slots need one barrier per row (the slot written next is never one of the three being read); the
+// 80-row form (Cout 5..8) keeps 3 slots inside the 64 KiB of static LDS and pays a second barrier.
+template <int MT, int KC>
+__global__ __launch_bounds__(256) void thin4_cout_kernel_rows(const T4Args a) {
+  constexpr int RING = MT >= 5 ? 3 : 4, NL = KC * 4;
+  __shared__ float P[RING][MT * 16][64];
+  const int lane = threadIdx.x & 63, p = lane & 15, g = lane >> 4;
+  const int wv_id = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const unsigned npix = (unsigned)(a.N * a.H * a.W);
+  const auto in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, (int)(npix * (unsigned)a.ld * 4u), 0x00020000);
+  const unsigned ldb = (unsigned)a.ld * 4u;
+  const int u = blockIdx.x;
+  const int xs = u % a.strips; const int r0 = u / a.strips;
+  const int yb = r0 % a.ybands, n = r0 / a.ybands;
+  const int col = 16 * wv_id + p;                      // P column of this lane: image column x0 - 1 + col
+  const int x = xs * 62 - 1 + col;
+  const int y0 = yb * a.rh;
+  const int y1 = y0 + a.rh < a.H ? y0 + a.rh : a.H;
+
+  // A operand: row 16 * t + p = (window position q, co), K index c = 64 * ch + 16 * j + 4 * g + e
+  f32x4 wA[MT][NL];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    const int row = 16 * t + p;
+    const int q = row / a.Cout, co = row - q * a.Cout;
+    const int tap = q < 9 ? a.tapidx[q] : -1;
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+      const int c0 = 16 * l + 4 * g;
+      const int k = a.kmode == 0 ? (c0 >> 4) * a.ntaps * 16 + tap * 16 + (c0 & 15) : tap * a.C + c0;
+      wA[t][l] = tap >= 0 ? *(const f32x4*)(a.w + (size_t)co * a.Kp + k) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  const unsigned coloff = (unsigned)x < (unsigned)a.W ? (unsigned)x * ldb + 16u * (unsigned)g : OOB;
+  const unsigned imgoff = (unsigned)(n * a.H) * (unsigned)a.W * ldb;
+  auto load_row = [&](f32x4* dst, int iy) {
+    const bool rok = (unsigned)iy < (unsigned)a.H && coloff != OOB;
+    const unsigned ro = imgoff + (unsigned)iy * (unsigned)a.W * ldb + coloff;
+#pragma unroll
+    for (int l = 0; l < NL; ++l) dst[l] = ldbuf4(in_rs, rok ? ro + 64u * (unsigned)l : OOB);
+  };
+  // the sum: lane group g owns output channel 4 * pass + g of pixel column `col`
+  const int cpad = (a.Cout + 3) & ~3;
+  const bool st_col = col >= 1 && col <= 62 && x < a.W;
+  unsigned tapmask = 0;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) tapmask |= (a.tapidx[q] >= 0 ? 1u : 0u) << q;
+  float bv[2];                                         // loaded here: a load inside the march would drain the prefetched row
+#pragma unroll
+  for (int h = 0; h < 2; ++h) bv[h] = (a.bias && 4 * h + g < a.Cout) ? a.bias[4 * h + g] : 0.f;
+
+  f32x4 xv[2][NL];
+  load_row(xv[0], y0 - 1);
+  const int nrows = y1 - y0 + 2;                       // input rows y0 - 1 .. y1
+  auto body = [&](int it, f32x4* cur, f32x4* nxt) {
+    if (it + 1 < nrows) load_row(nxt, y0 + it);
+    f32x4 acc[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int l = 0; l < NL; ++l)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int t = 0; t < MT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wA[t][l][e], cur[l][e], acc[t], 0, 0, 0);
+    float (*Ps)[64] = P[it % RING];
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Ps[16 * t + 4 * g + r][(col + 16 * ((r + g) & 3)) & 63] = acc[t][r];
+    __syncthreads();
+    if (it >= 2) {                                     // output row y0 + it - 2: window rows in slots it - 2, it - 1, it
+      const int y = y0 + it - 2;
+      const size_t pix = (size_t)(n * a.H + y) * a.W + x;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int co = 4 * h + g;
+        if (4 * h >= cpad) break;
+        const int cor = co < a.Cout ? co : a.Cout - 1;
+        float pv[9];                                   // all nine reads first, no branch between them
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+          const int row = q * a.Cout + cor;
+          pv[q] = P[(it - 2 + q / 3) % RING][row][(col + (q % 3 - 1) + 16 * ((row + (row >> 2)) & 3)) & 63];
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) s += ((tapmask >> q) & 1u) ? pv[q] : 0.f;    // a window position without a tap has no P row
+        if (co >= a.Cout) s = 0.f;
+        if (st_col) {
+          if (co < a.Cout) {
+            s += bv[h];
+            if (a.res) s += a.res[pix * a.ldr + co];
+            s = act_apply(s, a.act, a.slope);
+          }
+          a.out[pix * a.ldo + co] = s;                 // pad lanes [Cout, pad4) are written as 0
+        }
+      }
+    }
+    if (RING == 3) __syncthreads();
+  };
+  for (int it = 0; it < nrows; it += 2) {
+    body(it, xv[0], xv[1]);
+    if (it + 1 < nrows) body(it + 1, xv[1], xv[0]);
+  }
+}
+
+// (A streaming form of the 4x4x1 kernel -- a wave walking a column of bands with all 10 rows of a body in a register ring, every row
 //  requested a whole body before its first use -- was built and measured in round 2: 0.580 vs 0.585 ms at 16 x 512^2, 64 -> 3.
 //  Ablation builds: no MFMAs 0.520, every load from one cache-resident KiB 0.319, only the dx = 0 loads
 //  real 0.480: the time is issue (0.32) PLUS memory (0.16 unique + 0.10 for the overlapping dx loads), not latency.)
@@ -596,6 +719,20 @@ static bool routes_thin32(const ssg_conv_desc* d, int kind) {
   if (d->W < 32 || (long long)d->N * d->H * d->W < 65536) return false;          // 32-pixel strips: small images stay on the 4-pixel kernel
   for (int t = 0; t < d->ntaps; ++t) if (d->dy[t] || d->dx[t]) return true;       // a real window, not the 1x1 case
   return false;
+}
+
+// thin-Cout 3x3 on the rows form (thin4_cout_kernel_rows): the weights must fit the registers, MT * KC * 16 <= 128 per lane.
+// Returns MT (row tiles of 16) or 0 = stays on the 4x4x1 body: Cin 384 / 512 / 768 (the 64^2 .. 16^2 levels) and
+// 128 / 256 -> 6..8 would need 160 - 320 weight registers.
+static int rows_form_mt(const ssg_conv_desc* d, int kind, bool ks1) {
+  if (kind != 4 || ks1) return 0;
+  const int kc = d->C1 / 64;
+  if (kc != 1 && kc != 2 && kc != 4) return 0;
+  const int need = (9 * d->Cout + 15) / 16;
+  const int mt = need <= 2 ? 2 : need <= 3 ? 3 : 5;
+  if (mt * kc * 16 > 128 || (kc == 4 && mt != 2)) return 0;
+  if ((long long)d->N * d->H * d->W * d->ldo >= (1ll << 30) || (d->res && (long long)d->N * d->H * d->W * d->ldr >= (1ll << 30))) return 0;
+  return mt;
 }
 
 // profiling label: 12 = thin4_cin (4x4x1), 13 = thin4_cout, 14 = tiny4 (VALU), 15 = thin32_cin (32x32x2)
@@ -648,6 +785,23 @@ int ssg_thin4_conv_launch(const ssg_conv_desc* d, int kind, hipStream_t st) {
       if (nt) hipLaunchKernelGGL((thin32_cin_kernel<0, 1, true>), grid2, block, 0, st, a);
       else hipLaunchKernelGGL((thin32_cin_kernel<0, 1, false>), grid2, block, 0, st, a);
     }
+    SSG_LAUNCH_CHECK();
+    return SSG_OK;
+  }
+  if (const int mt = rows_form_mt(d, kind, ks1)) {
+    a.strips = (d->W + 61) / 62;
+    a.rh = 32;                                         // shorter bands (more halo rows) until the grid fills the machine
+    while (a.rh > 8 && (long long)d->N * ((d->H + a.rh - 1) / a.rh) * a.strips < 1024) a.rh >>= 1;
+    a.ybands = (d->H + a.rh - 1) / a.rh;
+    a.total_units = d->N * a.ybands * a.strips;
+    const dim3 gridr((unsigned)a.total_units);
+    const int kc = d->C1 / 64;
+    if (mt == 2 && kc == 1) hipLaunchKernelGGL((thin4_cout_kernel_rows<2, 1>), gridr, block, 0, st, a);
+    else if (mt == 2 && kc == 2) hipLaunchKernelGGL((thin4_cout_kernel_rows<2, 2>), gridr, block, 0, st, a);
+    else if (mt == 2) hipLaunchKernelGGL((thin4_cout_kernel_rows<2, 4>), gridr, block, 0, st, a);
+    else if (mt == 3 && kc == 1) hipLaunchKernelGGL((thin4_cout_kernel_rows<3, 1>), gridr, block, 0, st, a);
+    else if (mt == 3) hipLaunchKernelGGL((thin4_cout_kernel_rows<3, 2>), gridr, block, 0, st, a);
+    else hipLaunchKernelGGL((thin4_cout_kernel_rows<5, 1>), gridr, block, 0, st, a);
     SSG_LAUNCH_CHECK();
     return SSG_OK;
   }
