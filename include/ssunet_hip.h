@@ -515,6 +515,28 @@ int ssg_tool_mfma_peak_bf16_data(float* scratch, int blocks, int iters, const vo
 int ssg_tool_mfma_peak_bf16_data16(float* scratch, int blocks, int iters, const void* data, void* stream);   /* the same on v_mfma_f32_16x16x32_bf16 */
 int ssg_tool_copy_f32(const float* src, float* dst, int64_t n, void* stream);   /* one float4 per thread, non-temporal */
 
+/* ------------------------------------------------------------------ sliding-window inference (HBM-bound)
+ * The two host loops around the generator forward of aerial_image_segmentation_api.py, restated bit for bit.
+ * Origins: P pairs (h1, w1) of int32, top-left corners of p_size x p_size patches.  `org` is the DEVICE array the kernels
+ * read; `org_host` is the caller's HOST copy of the same values, which the entry point checks (every patch inside the
+ * H x W image) before it launches -- a patch outside the image is refused with SSG_EINVAL and nothing is enqueued.
+ *
+ * ssg_sw_gather_patches_u8_f32 (get_patched_input, api.py:336-373): img is [H][W][3] uint8 (BGR, 4-byte aligned); out is
+ * [P, 3, out_size, out_size] fp32 NHWC with ld = 4, pad lane written as 0.  p_size / out_size is 1 (the byte itself) or 2
+ * ((a + b + c + d + 2) >> 2 of the 2x2 box); then ((float)v - mean[c]) * rdenom[c], then / 255.0f, each one fp32 rounding.
+ * mean / rdenom are albumentations Normalize()'s fp32 mean * 255 and 1 / (std * 255), computed by the caller.
+ *
+ * ssg_sw_merge_masks_f32_u8 (patch_merge, api.py:119-217): probs is [P, C, S, S] fp32 NHWC with pixel stride ld,
+ * p_size / S is 1 or 2, weight[p] (int32, >= 0) is the number of times patch p counts; out is [C][H][W] uint8 in {0, 255}.
+ * Per pixel and class, over the patches that cover it: u8 = (uint8)(p * 255.0f), resized to p_size (2x: 0.25 / 0.75 taps,
+ * edge-clamped, rounded half up), counted if > 127; k = sum of the weights that counted, n = sum of the weights (0 -> 1);
+ * out = (int)((double)k / n * 255.0) > 127 ? 255 : 0.  One thread per pixel, no atomics: deterministic. */
+int ssg_sw_gather_patches_u8_f32(const uint8_t* img, int H, int W, const int32_t* org, const int32_t* org_host, int P,
+                                 int p_size, int out_size, float mean0, float mean1, float mean2,
+                                 float rdenom0, float rdenom1, float rdenom2, float* out, void* stream);
+int ssg_sw_merge_masks_f32_u8(const float* probs, int ld, int P, int C, int S, const int32_t* org, const int32_t* org_host,
+                              const int32_t* weight, int p_size, int H, int W, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,9 @@ scripts/aerial_image_segmentation_api.py -- SURVEY.md 8f row N2 / BASELINE confi
 
 GPU side: the eval-mode generator forward over all patches of an image.  The reference runs one patch per forward
 (`api.py:385-390`); here patches are batched and every BasicBlock runs as three MFMA launches with its batch norms folded
-in, then one sigmoid kernel -- same values, no per-patch sync.
+in, then one sigmoid kernel -- same values, no per-patch sync.  `segment_image` also runs the two host loops around the
+forwards (patch cutting / resizing / normalisation, and `patch_merge`) as HIP kernels, bit for bit what the host functions
+below compute; those stay as the oracle and for the ground-truth branch.
 
 Host side (numpy, no cv2 / albumentations -- neither is installed here, and the package takes on no host dependency for
 them): `load_segmentation_models` (`api.py:302-333`), `get_patched_input` (`api.py:336-373`, including its double
@@ -259,6 +261,52 @@ def patch_merge(img, masks, p_size, config, p_overlap):
         full = (np.divide(merged, div) * 255).astype('uint8')
         all_class_mask.append(post_process_resized_mask(full))
     return all_class_mask
+
+
+# ----------------------------------------------------------------------------- the whole pipeline on the device
+def unique_origins(org):
+    """(distinct origins of `org` in order of first appearance, how often each occurs).  The four corner-anchored sweeps of
+    `patch_origins` coincide whenever (image - patch) is a multiple of the step: at the shipped geometry (2048^2, patch 1024,
+    overlap 0.5) the 36 patches have 9 distinct origins, each four times."""
+    count = {}
+    for o in org:
+        o = (int(o[0]), int(o[1]))
+        count[o] = count.get(o, 0) + 1                   # dicts keep insertion order
+    return list(count.keys()), list(count.values())
+
+
+def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_probs=False):
+    """`segmentation_inference_full(model, *get_patched_input(...), config, False)[0]` for an image already in memory, with
+    everything between the uint8 image and the uint8 masks on the device: the image is uploaded once, each batch of patches is
+    cut, resized and normalised by `ops.sw_gather_patches`, `sigmoid(model(x))` stays on the device, `ops.sw_merge_masks` does
+    `patch_merge`, and num_classes * H * W bytes come back.  Returns a list of num_classes uint8 [H, W] masks in {0, 255}.
+    `dedupe`: infer each distinct origin once and let it enter the merge with its multiplicity (the same masks whenever
+    equal patches give equal probabilities, which they do inside one batch composition).
+    `return_probs`: also return (the host copy [P, C, S, S] of the probabilities that were merged, their origins, their weights).
+    Not covered, as on the host path they stay with: the ground-truth branch, PNG decoding, non-square inference sizes and
+    resize factors other than 1 and 2."""
+    p_size, size, overlap, classes = config['patch_size'], config['input_w'], config['patch_overlap'], config['num_classes']
+    if (config['input_h'], config['input_w']) != (size, size):
+        raise NotImplementedError('non-square inference size')
+    img_bgr = np.asarray(img_bgr)
+    if img_bgr.dtype != np.uint8 or img_bgr.ndim != 3 or img_bgr.shape[2] != 3:
+        raise TypeError('segment_image expects an HxWx3 uint8 image')
+    img_h, img_w = img_bgr.shape[0], img_bgr.shape[1]
+    org = patch_origins(img_h, img_w, p_size, overlap)
+    org, weights = unique_origins(org) if dedupe else (org, [1] * len(org))
+    dev = next(model.parameters()).device
+    img = torch.from_numpy(np.ascontiguousarray(img_bgr)).to(dev)
+    probs = ops.new_nhwc(len(org), classes, size, size, dev)
+    model.eval()
+    with torch.no_grad():
+        for i in range(0, len(org), batch_size):
+            x = ops.sw_gather_patches(img, org[i:i + batch_size], p_size, size)
+            ops.sigmoid_into(model(x), probs[i:i + batch_size])
+        masks = ops.sw_merge_masks(probs, org, weights, p_size, img_h, img_w).cpu().numpy()
+    masks = [masks[c] for c in range(classes)]
+    if return_probs:
+        return masks, probs.cpu().contiguous().numpy(), org, weights
+    return masks
 
 
 def load_segmentation_models(config_file):

@@ -1,0 +1,187 @@
+// Sliding-window inference around the generator forward (aerial_image_segmentation_api.py, BASELINE config 5), HBM-bound:
+//   sw_gather_kernel: uint8 BGR image + patch origins -> network input (crop, 2x2 box resize, double normalisation), NHWC ld 4;
+//   sw_merge_kernel:  per-patch probabilities -> {0, 255} class masks at image resolution (uint8 round trip, 2x bilinear,
+//                     threshold, overlap vote, threshold).
+// Both restate integer / single-rounding arithmetic of the host functions get_patched_input and patch_merge and are meant
+// to match them bit for bit.  ABI: include/ssunet_hip.h.
+#include "common.h"
+
+namespace {
+
+// Dword `idx` of the image as an aligned load; the last, partial dword of an image whose byte count is no multiple of 4 is put
+// together from its bytes, and anything beyond reads as 0: no byte outside [0, total) is touched.
+__device__ __forceinline__ uint32_t sw_ldw(const uint8_t* __restrict__ img, long long idx, long long total) {
+  const long long b = idx * 4;
+  if (b + 4 <= total) return *(const uint32_t*)(img + b);
+  uint32_t v = 0;
+  for (int k = 0; k < 4; ++k)
+    if (b + k < total) v |= (uint32_t)img[b + k] << (8 * k);
+  return v;
+}
+
+// The NB (3 or 6) bytes at byte offset `b` (any alignment) as two dwords, from aligned loads.
+template <int NB>
+__device__ __forceinline__ void sw_bytes(const uint8_t* __restrict__ img, long long b, long long total, uint32_t& lo, uint32_t& hi) {
+  const long long a = b >> 2;
+  const int sh = 8 * (int)(b & 3);
+  const uint32_t d0 = sw_ldw(img, a, total), d1 = sw_ldw(img, a + 1, total);
+  lo = (uint32_t)((((uint64_t)d1 << 32) | d0) >> sh);
+  hi = 0;
+  if (NB > 4) {
+    const uint32_t d2 = sw_ldw(img, a + 2, total);          // 3 + 6 bytes span at most three dwords
+    hi = (uint32_t)((((uint64_t)d2 << 32) | d1) >> sh);
+  }
+}
+
+// One thread per output pixel, lanes along the patch row: every store is one 16-byte pixel, 1 KiB contiguous per wave.
+// F = p_size / out_size.  The origin of the block's patch is wave-uniform (scalar loads, once per thread).
+template <int F>
+__global__ __launch_bounds__(256) void sw_gather_kernel(const uint8_t* __restrict__ img, int H, int W, const int32_t* __restrict__ org,
+                                                        int out_size, int nb, float m0, float m1, float m2, float r0, float r1, float r2,
+                                                        float* __restrict__ out) {
+  const int p = (int)(blockIdx.x / (unsigned)nb);
+  const int i = (int)(blockIdx.x % (unsigned)nb) * 256 + (int)threadIdx.x;
+  if (i >= out_size * out_size) return;
+  const int h1 = org[2 * p], w1 = org[2 * p + 1];
+  if (h1 < 0 || w1 < 0 || h1 > H - out_size * F || w1 > W - out_size * F) return;   // the entry point checked its host copy; never read outside
+  const int oy = i / out_size, ox = i - oy * out_size;
+  const long long total = (long long)H * W * 3;
+  uint32_t v[3];
+  if (F == 1) {
+    uint32_t lo, hi;
+    sw_bytes<3>(img, ((long long)(h1 + oy) * W + (w1 + ox)) * 3, total, lo, hi);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = (lo >> (8 * c)) & 255u;
+  } else {
+    uint32_t lo0, hi0, lo1, hi1;
+    const long long b = ((long long)(h1 + 2 * oy) * W + (w1 + 2 * ox)) * 3;
+    sw_bytes<6>(img, b, total, lo0, hi0);
+    sw_bytes<6>(img, b + (long long)W * 3, total, lo1, hi1);
+    const uint64_t t = ((uint64_t)hi0 << 32) | lo0, u = ((uint64_t)hi1 << 32) | lo1;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)                              // resize_u8 at 1/2: (a + b + c + d + 2) >> 2
+      v[c] = ((uint32_t)((t >> (8 * c)) & 255u) + (uint32_t)((t >> (8 * c + 24)) & 255u) +
+              (uint32_t)((u >> (8 * c)) & 255u) + (uint32_t)((u >> (8 * c + 24)) & 255u) + 2u) >> 2;
+  }
+  // normalize_imagenet then / 255: subtract, multiply, divide -- three correctly rounded fp32 operations, none fusable
+  f32x4 o;
+  o[0] = (((float)v[0] - m0) * r0) / 255.0f;
+  o[1] = (((float)v[1] - m1) * r1) / 255.0f;
+  o[2] = (((float)v[2] - m2) * r2) / 255.0f;
+  o[3] = 0.f;
+  *(f32x4*)(out + ((size_t)p * out_size * out_size + i) * 4) = o;
+}
+
+// (uint8)(p * 255) of patch_merge for p in [0, 1]
+__device__ __forceinline__ int sw_u8(float p) { return (int)(p * 255.0f) & 255; }
+
+// One thread per image pixel, one block per 256-pixel piece of an image row; for each class quad a thread walks the patches and
+// counts, with the patch's weight, those whose resized uint8 map exceeds 127 at its pixel.  Gather form: no atomics, every output
+// byte has one writer.  The origin / weight lists are read 64 entries at a time, one entry per lane, and handed round the wave
+// with v_readlane: the patch loop itself reads no list from memory, and a patch that misses the block's row is skipped by a
+// scalar branch.  F = p_size / S; at F = 2 the four taps of resize_u8's 2x bilinear carry weights (9, 3, 3, 1) / 16, so
+// floor(v + 0.5) > 127  <=>  9a + 3b + 3c + d >= 2040 in integers.
+template <int F>
+__global__ __launch_bounds__(256) void sw_merge_kernel(const float* __restrict__ probs, int ld, int P, int C, int S,
+                                                       const int32_t* __restrict__ org, const int32_t* __restrict__ wt, int H, int W, int nbx,
+                                                       uint8_t* __restrict__ out) {
+  const int y = (int)(blockIdx.x / (unsigned)nbx);
+  const int x = (int)(blockIdx.x % (unsigned)nbx) * 256 + (int)threadIdx.x;
+  const int lane = (int)threadIdx.x & 63;
+  const int p_size = S * F;
+  for (int c0 = 0; c0 < C; c0 += 4) {
+    int k[4] = {0, 0, 0, 0}, n = 0;
+    for (int base = 0; base < P; base += 64) {
+      int vh = 0, vw = 0, vm = 0;
+      if (base + lane < P) {
+        vh = org[2 * (base + lane)];
+        vw = org[2 * (base + lane) + 1];
+        vm = wt[base + lane];
+      }
+      const int cnt = P - base < 64 ? P - base : 64;
+      for (int j = 0; j < cnt; ++j) {
+        const int h1 = __builtin_amdgcn_readlane(vh, j), w1 = __builtin_amdgcn_readlane(vw, j), m = __builtin_amdgcn_readlane(vm, j);
+        const int ly = y - h1;
+        if (ly < 0 || ly >= p_size || m == 0) continue;                   // wave-uniform
+        const int lx = x - w1;
+        if (x >= W || lx < 0 || lx >= p_size) continue;
+        const float* pp = probs + (size_t)(base + j) * S * S * ld + c0;
+        int hit[4];
+        if (F == 1) {
+          const f32x4 a = *(const f32x4*)(pp + ((size_t)ly * S + lx) * ld);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) hit[e] = sw_u8(a[e]) > 127;
+        } else {
+          // resize_u8 at 2: output 2i blends (i - 1, i), output 2i + 1 blends (i, i + 1), 0.25 / 0.75, clamped at the edges
+          const int iy = ly >> 1, ix = lx >> 1;
+          const int jy = (ly & 1) ? (iy + 1 < S ? iy + 1 : S - 1) : (iy > 0 ? iy - 1 : 0);
+          const int jx = (lx & 1) ? (ix + 1 < S ? ix + 1 : S - 1) : (ix > 0 ? ix - 1 : 0);
+          const f32x4 a = *(const f32x4*)(pp + ((size_t)iy * S + ix) * ld), b = *(const f32x4*)(pp + ((size_t)iy * S + jx) * ld);
+          const f32x4 c = *(const f32x4*)(pp + ((size_t)jy * S + ix) * ld), d = *(const f32x4*)(pp + ((size_t)jy * S + jx) * ld);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) hit[e] = 9 * sw_u8(a[e]) + 3 * sw_u8(b[e]) + 3 * sw_u8(c[e]) + sw_u8(d[e]) >= 2040;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) k[e] += hit[e] ? m : 0;
+        n += m;
+      }
+    }
+    if (x < W) {
+      const double dn = (double)(n == 0 ? 1 : n);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (c0 + e < C)                                                   // patch_merge's own fp64 operations: (merged / div * 255) -> uint8 -> > 127
+          out[((size_t)(c0 + e) * H + y) * W + x] = (int)((double)k[e] / dn * 255.0) > 127 ? 255 : 0;
+    }
+  }
+}
+
+// host copy of the origin list: every patch inside the image
+int sw_check_origins(const int32_t* org_host, int P, int p_size, int H, int W, const char* who) {
+  for (int p = 0; p < P; ++p) {
+    const int h1 = org_host[2 * p], w1 = org_host[2 * p + 1];
+    SSG_REQUIRE(h1 >= 0 && w1 >= 0 && h1 <= H - p_size && w1 <= W - p_size, SSG_EINVAL,
+                "%s: patch %d at (%d, %d), size %d, lies outside the %d x %d image", who, p, h1, w1, p_size, H, W);
+  }
+  return SSG_OK;
+}
+
+}  // namespace
+
+extern "C" int ssg_sw_gather_patches_u8_f32(const uint8_t* img, int H, int W, const int32_t* org, const int32_t* org_host, int P,
+                                            int p_size, int out_size, float mean0, float mean1, float mean2,
+                                            float rdenom0, float rdenom1, float rdenom2, float* out, void* stream) {
+  SSG_REQUIRE(img && org && org_host && out, SSG_EINVAL, "sw_gather: null pointer");
+  SSG_REQUIRE(P > 0 && H > 0 && W > 0 && p_size > 0 && out_size > 0, SSG_EINVAL, "sw_gather: bad sizes (P %d, image %d x %d, patch %d -> %d)", P, H, W, p_size, out_size);
+  SSG_REQUIRE(p_size == out_size || p_size == 2 * out_size, SSG_EINVAL, "sw_gather: patch %d -> %d: only the factors 1 and 2 are built", p_size, out_size);
+  if (int rc = sw_check_origins(org_host, P, p_size, H, W, "sw_gather")) return rc;
+  SSG_REQUIRE((((uintptr_t)img) & 3) == 0 && ssg_aligned16(out) && (((uintptr_t)org) & 3) == 0, SSG_EALIGN, "sw_gather: image 4-byte, output 16-byte aligned");
+  const long long nb = ssg_cdiv((long long)out_size * out_size, 256);
+  SSG_REQUIRE((long long)out_size * out_size < (1ll << 31) && nb * P < (1ll << 31), SSG_EINVAL, "sw_gather: too large");
+  const dim3 grid((unsigned)(nb * P));
+  if (p_size == out_size)
+    hipLaunchKernelGGL(sw_gather_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, img, H, W, org, out_size, (int)nb, mean0, mean1, mean2, rdenom0, rdenom1, rdenom2, out);
+  else
+    hipLaunchKernelGGL(sw_gather_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, img, H, W, org, out_size, (int)nb, mean0, mean1, mean2, rdenom0, rdenom1, rdenom2, out);
+  SSG_LAUNCH_CHECK();
+  return SSG_OK;
+}
+
+extern "C" int ssg_sw_merge_masks_f32_u8(const float* probs, int ld, int P, int C, int S, const int32_t* org, const int32_t* org_host,
+                                         const int32_t* weight, int p_size, int H, int W, uint8_t* out, void* stream) {
+  SSG_REQUIRE(probs && org && org_host && weight && out, SSG_EINVAL, "sw_merge: null pointer");
+  SSG_REQUIRE(P > 0 && C > 0 && S > 0 && H > 0 && W > 0 && p_size > 0, SSG_EINVAL, "sw_merge: bad sizes (P %d, C %d, S %d, image %d x %d, patch %d)", P, C, S, H, W, p_size);
+  SSG_REQUIRE(p_size == S || p_size == 2 * S, SSG_EINVAL, "sw_merge: %d -> patch %d: only the factors 1 and 2 are built", S, p_size);
+  SSG_REQUIRE(ld % 4 == 0 && ld >= C, SSG_EALIGN, "sw_merge: ld %d for %d classes", ld, C);
+  if (int rc = sw_check_origins(org_host, P, p_size, H, W, "sw_merge")) return rc;
+  SSG_REQUIRE(ssg_aligned16(probs) && (((uintptr_t)org) & 3) == 0 && (((uintptr_t)weight) & 3) == 0, SSG_EALIGN, "sw_merge: probabilities 16-byte aligned");
+  const long long nbx = ssg_cdiv(W, 256);
+  SSG_REQUIRE(nbx * H < (1ll << 31), SSG_EINVAL, "sw_merge: too large");
+  const dim3 grid((unsigned)(nbx * H));
+  if (p_size == S)
+    hipLaunchKernelGGL(sw_merge_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, probs, ld, P, C, S, org, weight, H, W, (int)nbx, out);
+  else
+    hipLaunchKernelGGL(sw_merge_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, probs, ld, P, C, S, org, weight, H, W, (int)nbx, out);
+  SSG_LAUNCH_CHECK();
+  return SSG_OK;
+}

@@ -1341,6 +1341,95 @@ def gaussian(x):
     return _Unary.apply(x, UNARY_GAUSSIAN)
 
 
+def sigmoid_into(x, out):
+    """sigmoid(x) written into `out`, an NHWC tensor of x's shape (or a batch slice of one) -- inference only, no autograd:
+    the launch of `sigmoid` with another destination."""
+    _lib.require_gpu(x)
+    _lib.require_gpu(out)
+    x = to_nhwc(x.detach())
+    if out.shape != x.shape:
+        raise ValueError('sigmoid_into: out is %s, x is %s' % (tuple(out.shape), tuple(x.shape)))
+    n, c, h, w = x.shape
+    call('ssg_unary_fwd_f32', ptr(x), _ld(x), n * h * w, c, UNARY_SIGMOID, ptr(out), _ld(out), stream_ptr())
+    return out
+
+
+# ----------------------------------------------------------------------------- sliding-window inference (csrc/sliding_window.hip)
+_SW_NORM = []
+
+
+def _sw_norm_consts():
+    """mean * 255 and 1 / (std * 255) of albumentations Normalize(): the numpy expressions of
+    aerial_image_segmentation_api.normalize_imagenet, so that the kernel multiplies by the very same fp32 values."""
+    if not _SW_NORM:
+        import numpy as np
+        mean = np.array((0.485, 0.456, 0.406), dtype=np.float32) * 255.0
+        std = np.array((0.229, 0.224, 0.225), dtype=np.float32) * 255.0
+        denom = np.reciprocal(std, dtype=np.float32)
+        _SW_NORM.append([float(v) for v in mean] + [float(v) for v in denom])
+    return _SW_NORM[0]
+
+
+def _sw_origins(origins, device):
+    """(host int32 [P, 2] tensor, its device copy) of a list of patch origins (h1, w1): the entry points check the host copy
+    and the kernels read the device one."""
+    host = torch.as_tensor(origins, dtype=torch.int32, device='cpu').contiguous()
+    if host.dim() != 2 or host.shape[1] != 2 or host.shape[0] == 0:
+        raise ValueError('origins: expected P >= 1 pairs (h1, w1), got shape %s' % (tuple(host.shape),))
+    return host, host.to(device)
+
+
+def _sw_factor(p_size, size, who):
+    if size <= 0 or p_size not in (size, 2 * size):
+        raise NotImplementedError('%s: patch %d at %d: only the exact factors 1 and 2 are built' % (who, p_size, size))
+
+
+def _sw_inside(host, p_size, img_h, img_w, who):
+    h1, w1 = host[:, 0], host[:, 1]
+    if bool(((h1 < 0) | (w1 < 0) | (h1 > img_h - p_size) | (w1 > img_w - p_size)).any()):
+        raise ValueError('%s: a patch of size %d lies outside the %d x %d image' % (who, p_size, img_h, img_w))
+
+
+def sw_gather_patches(img_u8, origins, p_size, out_size):
+    """Network input of the sliding-window pipeline from the image on the device: for every origin (h1, w1) the
+    p_size x p_size crop of `img_u8` ([H, W, 3] uint8, BGR), resized to out_size (p_size / out_size in {1, 2}), normalised
+    and divided by 255 exactly as `get_patched_input` does on the host.  Returns [P, 3, out_size, out_size] fp32 NHWC
+    (ld 4, pad lane 0).  `origins`: P pairs (h1, w1)."""
+    _lib.require_gpu(img_u8)
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3 or not img_u8.is_contiguous():
+        raise TypeError('sw_gather_patches: expected a contiguous [H, W, 3] uint8 image, got %s %s' % (img_u8.dtype, tuple(img_u8.shape)))
+    _sw_factor(p_size, out_size, 'sw_gather_patches')
+    host, devo = _sw_origins(origins, img_u8.device)
+    img_h, img_w = img_u8.shape[0], img_u8.shape[1]
+    _sw_inside(host, p_size, img_h, img_w, 'sw_gather_patches')
+    n = host.shape[0]
+    out = new_nhwc(n, 3, out_size, out_size, img_u8.device)
+    call('ssg_sw_gather_patches_u8_f32', ptr(img_u8), img_h, img_w, ptr(devo), ptr(host), n, p_size, out_size,
+         *(_sw_norm_consts() + [ptr(out), stream_ptr()]))
+    return out
+
+
+def sw_merge_masks(probs, origins, weights, p_size, img_h, img_w):
+    """`patch_merge` on the device: probs [P, C, S, S] fp32 (NHWC, as `sigmoid(model(x))` leaves them; p_size / S in {1, 2}),
+    one origin and one int weight (multiplicity) per patch -> [C, img_h, img_w] uint8 masks in {0, 255}."""
+    _lib.require_gpu(probs)
+    if probs.dim() != 4 or probs.shape[2] != probs.shape[3]:
+        raise ValueError('sw_merge_masks: expected [P, C, S, S] probabilities, got %s' % (tuple(probs.shape),))
+    probs = to_nhwc(probs.detach())
+    n, c, s, _ = probs.shape
+    _sw_factor(p_size, s, 'sw_merge_masks')
+    host, devo = _sw_origins(origins, probs.device)
+    wt = torch.as_tensor(weights, dtype=torch.int32, device='cpu').contiguous()
+    if host.shape[0] != n or wt.shape != (n,) or bool((wt < 0).any()):
+        raise ValueError('sw_merge_masks: %d patches need %d origins and %d non-negative weights' % (n, n, n))
+    _sw_inside(host, p_size, img_h, img_w, 'sw_merge_masks')
+    out = torch.empty((c, img_h, img_w), dtype=torch.uint8, device=probs.device)
+    wdev = wt.to(probs.device)
+    call('ssg_sw_merge_masks_f32_u8', ptr(probs), _ld(probs), n, c, s, ptr(devo), ptr(host), ptr(wdev),
+         p_size, img_h, img_w, ptr(out), stream_ptr())
+    return out
+
+
 class _Mul(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):

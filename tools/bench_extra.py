@@ -1,11 +1,13 @@
 """Throughput of the rows beside the headline path (per-op A11/A12), one JSON
 object per line.  Not the graded metric (that is bench.py); these are the measurements DESIGN.md quotes for them.
-Usage (GPU box): python tools/bench_extra.py"""
+Usage (GPU box): python tools/bench_extra.py            (every row)
+                 python tools/bench_extra.py sw         (only the sliding-window pipeline rows)"""
 import json
 import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -26,17 +28,82 @@ def timed(fn, warm, n):
     return (time.perf_counter() - t0) / n
 
 
+def event_ms(fn, warm, n):
+    """HIP-event time of one fn() in ms (fn only enqueues)."""
+    for _ in range(warm):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / n
+
+
+def sliding_window_rows(G):
+    """C5 end to end from the in-memory uint8 image: one 2048^2 image, patch 1024, overlap 0.5, inference at 512^2."""
+    A, ops, L = S.aerial_image_segmentation_api, S.ops, S._lib
+    cfg = dict(patch_size=1024, input_w=512, input_h=512, patch_overlap=0.5, num_classes=3)
+    img = np.random.default_rng(5).integers(0, 256, (2048, 2048, 3), dtype=np.uint8)
+
+    def host_path():
+        full, patches, masks = A.get_patched_input('image', cfg, False, imread=lambda p: img)
+        return A.segmentation_inference_full(G, full, patches, masks, cfg, False, batch_size=12)[0]
+    t_host = timed(host_path, 1, 2)
+    t_dev = timed(lambda: A.segment_image(G, img, cfg, batch_size=12, dedupe=False), 1, 3)
+    t_dedupe = timed(lambda: A.segment_image(G, img, cfg, batch_size=12, dedupe=True), 1, 3)
+    out = [{'what': 'C5 one 2048^2 uint8 image -> 3 class masks, patch 1024 / overlap 0.5 / inference 512^2, batch 12, from the in-memory array',
+            's_per_image_host_gather_and_merge': round(t_host, 3), 's_per_image_segment_image': round(t_dev, 4),
+            's_per_image_segment_image_dedupe': round(t_dedupe, 4)}]
+    # the two kernels alone (HIP events), for all 36 patches and for the 9 distinct ones, against the forwards they surround
+    dimg = torch.from_numpy(img).to(dev)
+    org36 = A.patch_origins(2048, 2048, 1024, 0.5)
+    org9, w9 = A.unique_origins(org36)
+    consts = ops._sw_norm_consts()
+    row = {'what': 'C5 sliding-window kernels alone (HIP events) and the batch-12 forwards between them, input resident'}
+    for name, org, wts in (('36', org36, [1] * 36), ('9', org9, w9)):
+        host, devo = ops._sw_origins(org, dev)
+        n = len(org)
+        x = ops.new_nhwc(n, 3, 512, 512, dev)
+        probs = ops.new_nhwc(n, 3, 512, 512, dev)
+        probs.copy_(torch.rand(n, 3, 512, 512, generator=torch.Generator().manual_seed(9)))
+        wdev = torch.tensor(wts, dtype=torch.int32).to(dev)
+        masks = torch.empty((3, 2048, 2048), dtype=torch.uint8, device=dev)
+        ms_g = event_ms(lambda: L.call('ssg_sw_gather_patches_u8_f32', L.ptr(dimg), 2048, 2048, L.ptr(devo), L.ptr(host), n, 1024, 512,
+                                       *(consts + [L.ptr(x), L.stream_ptr()])), 10, 1000)
+        ms_m = event_ms(lambda: L.call('ssg_sw_merge_masks_f32_u8', L.ptr(probs), 4, n, 3, 512, L.ptr(devo), L.ptr(host), L.ptr(wdev),
+                                       1024, 2048, 2048, L.ptr(masks), L.stream_ptr()), 10, 1000)
+        row['ms_gather_%s_patches' % name] = round(ms_g, 4)
+        row['ms_merge_%s_patches' % name] = round(ms_m, 4)
+        row['gather_%s_write_gb_per_s' % name] = round(n * 512 * 512 * 16 / ms_g / 1e6, 1)
+        row['merge_%s_read_gb_per_s' % name] = round(n * 512 * 512 * 16 / ms_m / 1e6, 1)
+        if n == 36:
+            G.eval()
+            with torch.no_grad():
+                dt = timed(lambda: [ops.sigmoid(G(x[i:i + 12])) for i in range(0, 36, 12)], 1, 3)
+            row['ms_36_forwards_batch_12'] = round(dt * 1e3, 2)
+        del x, probs
+    out.append(row)
+    return out
+
+
 def main():
     g = torch.Generator().manual_seed(7)
     out = []
     # C5: eval-mode generator over the 36 patches of a 2048^2 image (patches resized to 512^2), batched
     torch.manual_seed(41)
     G = S.models_seg_gan.Generator(dict(arch='UNet_R_SS_v2', num_classes=3, input_channels=3, deep_supervision=False)).to(dev)
+    if sys.argv[1:] == ['sw']:
+        for o in sliding_window_rows(G):
+            print(json.dumps(o), flush=True)
+        return
     patches = torch.randn(36, 3, 512, 512, generator=g)
     for bs in (1, 12):
         dt = timed(lambda: S.aerial_image_segmentation_api.infer_patches(G, patches, batch_size=bs), 1, 3)
         out.append({'what': 'C5 sliding-window inference, 36 x 3x512x512 patches, eval-mode G (BN folded), batch %d, incl. H2D/D2H' % bs,
                     'patches_per_s': round(36 / dt, 2), 's_per_image': round(dt, 3)})
+    out += sliding_window_rows(G)
     # batch 1 on resident inputs: kernel-by-kernel launches vs hipGraph replay (what the launch path costs at batch 1)
     xb = patches[:1].to(dev)
     G.eval()
