@@ -454,6 +454,17 @@ int ssg_dwconv2d_fwd_f32(const float* in, int N, int H, int W, int C, int ld, co
 int ssg_dwconv2d_dgrad_f32(const float* dout, int lddo, int N, int H, int W, int C, const float* w, int KH, int KW, int stride,
                            int pad_top, int pad_left, int OH, int OW, float* dx, int lddx, void* stream);
 int64_t ssg_dwconv2d_wgrad_workspace_bytes(int N, int OH, int OW, int C, int KH, int KW);
+/* ssg_dwconv2d_kernel_id: the kernel the three entry points above launch (the function they themselves switch on; test and
+ * profiling labels).  op: 0 = fwd, 1 = dgrad, 2 = wgrad; pad_left as passed to the entry point; NDH = N * rows of the tensor
+ * the call writes (N*OH for fwd, N*H for dgrad; unused by wgrad); aligned16 = both tensor pointers are 16-byte aligned
+ * (unused by wgrad).  Returns -1 for another op, else
+ *   fwd  :  0 = dw_fwd_kernel (generic),  1 = dw_s1_kernel<KW,T,1> (stride 1, KW in {3,5,7,9}),
+ *           2 = dw_s1_kernel<KW,T,2> (stride 2, KH == KW in {3,5});
+ *   dgrad: 10 = dw_dgrad_kernel (generic), 11 = dw_s1_kernel<KW,T,1> on the flipped kernel with pads K-1-pad,
+ *          12 / 13 = dw_dgrad_s2_kernel<KW,T,PLODD = 0 / 1> (pad_left even / odd);
+ *   wgrad: 20 = dw_wgrad_partial_kernel (generic), 21 / 22 = dw_wgrad_s1_kernel<KW,T,S = 1 / 2>;
+ * the tiled fwd / dgrad kernels need aligned16, NDH <= 65535 and (C/4 + 15)/16 <= 65535 (grid.y / grid.z). */
+int ssg_dwconv2d_kernel_id(int op, int stride, int KH, int KW, int pad_left, int64_t NDH, int C, int aligned16);
 int ssg_dwconv2d_wgrad_f32(const float* in, int N, int H, int W, int C, int ld, const float* dout, int lddo, int KH, int KW,
                            int stride, int pad_top, int pad_left, int OH, int OW, float* dw, void* ws, void* stream);
 /* element-wise: swish x*sigmoid(x) with the reference's backward (efficientnet_pytorch/utils.py:37-48),

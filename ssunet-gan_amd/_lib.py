@@ -139,6 +139,7 @@ SIGNATURES = {
     'ssg_dwconv2d_fwd_f32': [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P],
     'ssg_dwconv2d_dgrad_f32': [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P],
     'ssg_dwconv2d_wgrad_workspace_bytes': [_I, _I, _I, _I, _I, _I],
+    'ssg_dwconv2d_kernel_id': [_I, _I, _I, _I, _I, _L, _I, _I],
     'ssg_dwconv2d_wgrad_f32': [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     'ssg_unary_fwd_f32': [_P, _I, _L, _I, _I, _P, _I, _P],
     'ssg_unary_bwd_f32': [_P, _I, _P, _I, _L, _I, _I, _P, _I, _P],
@@ -197,10 +198,10 @@ _RESTYPES = {
     'ssg_conv2d_thin_bf16_wgrad_workspace_bytes': C.c_int64,
     'ssg_bn_stats_from_partials_workspace_bytes': C.c_int64,
 }
-_NO_STATUS = set(_RESTYPES) | {'ssg_abi_version', 'ssg_conv2d_split_bn', 'ssg_conv2d_in_affine_ok', 'ssg_conv2d_wgrad_in_affine_ok', 'ssg_conv2d_bwd_stats_ok', 'ssg_conv2d_kernel_id', 'ssg_conv2d_bnpart_rows', 'ssg_conv2d_wgrad_kernel_id',
+_NO_STATUS = set(_RESTYPES) | {'ssg_abi_version', 'ssg_conv2d_split_bn', 'ssg_conv2d_in_affine_ok', 'ssg_conv2d_wgrad_in_affine_ok', 'ssg_conv2d_bwd_stats_ok', 'ssg_conv2d_kernel_id', 'ssg_conv2d_bnpart_rows', 'ssg_conv2d_wgrad_kernel_id', 'ssg_dwconv2d_kernel_id',
                                 'ssg_spade_conv_modulate_ok', 'ssg_se_gate_ok'}
 
-ABI_VERSION = 9          # ssg_abi_version() of the library this ctypes table (ConvDesc layout, SIGNATURES) was written against
+ABI_VERSION = 10         # ssg_abi_version() of the library this ctypes table (ConvDesc layout, SIGNATURES) was written against
 
 _lib = None
 

@@ -149,6 +149,25 @@ struct DwS1Args {
 };
 constexpr int DW_XT = 4;
 
+// The one place that decides which kernel a depthwise call runs (exported as ssg_dwconv2d_kernel_id; the ids are listed in
+// include/ssunet_hip.h).  The three launchers below switch on its result, so a query cannot drift from what is launched.
+// `pl` is the call's pad_left (its parity picks the stride-2 input-gradient form), `NDH` = N * rows of the tensor the kernel
+// writes (grid.y of the tiled kernels), `aligned16` = both tensor pointers are 16-byte aligned.  The weight gradient reads
+// its rows through `ld4` alone and has no grid.y, so neither of the last two bears on it.
+enum { DW_OP_FWD = 0, DW_OP_DGRAD = 1, DW_OP_WGRAD = 2 };
+enum { DW_FWD_GENERIC = 0, DW_FWD_S1 = 1, DW_FWD_S2 = 2, DW_DGRAD_GENERIC = 10, DW_DGRAD_S1_FLIP = 11, DW_DGRAD_S2_EVEN = 12,
+       DW_DGRAD_S2_ODD = 13, DW_WGRAD_GENERIC = 20, DW_WGRAD_S1 = 21, DW_WGRAD_S2 = 22 };
+int dw_route(int op, int stride, int KH, int KW, int pl, long long NDH, int C, bool aligned16) {
+  const bool k35 = KW == 3 || KW == 5, k3579 = k35 || KW == 7 || KW == 9;
+  if (op == DW_OP_WGRAD) return stride == 1 && k3579 ? DW_WGRAD_S1 : (stride == 2 && k35 ? DW_WGRAD_S2 : DW_WGRAD_GENERIC);
+  if (op != DW_OP_FWD && op != DW_OP_DGRAD) return -1;
+  const bool fits = aligned16 && NDH <= 65535 && (C / 4 + 15) / 16 <= 65535;      // 16-byte rows; grid.y / grid.z limits
+  const bool s1 = fits && stride == 1 && k3579;
+  const bool s2 = fits && stride == 2 && KH == KW && k35;                         // k3 / k5: the shapes EfficientNet has
+  if (op == DW_OP_FWD) return s1 ? DW_FWD_S1 : (s2 ? DW_FWD_S2 : DW_FWD_GENERIC);
+  return s1 ? DW_DGRAD_S1_FLIP : (s2 ? ((pl & 1) ? DW_DGRAD_S2_ODD : DW_DGRAD_S2_EVEN) : DW_DGRAD_GENERIC);
+}
+
 // S = 2 (round 3): the same tiling for the stride-2 forward (the four stage transitions of an EfficientNet, 259 us each at B4 /
 // 1024^2 on the one-thread-per-output kernel): a thread's 4 outputs read (XT - 1) * 2 + KW source columns per kernel row.
 template <int KW, typename T, int S = 1>
@@ -204,13 +223,10 @@ int launch_dw_s1(const DwS1Args<T>& a, hipStream_t st) {
   SSG_LAUNCH_CHECK();
   return SSG_OK;
 }
-// stride-2 forward (k3 / k5: the shapes EfficientNet has); -1 = not covered
+// stride-2 forward (dw_route: KW is 3 or 5)
 template <typename T>
 int dw_s2_fwd_dispatch(const DwS1Args<T>& a, int KW, hipStream_t st) {
-  if ((long long)a.N * a.DH > 65535 || (a.C / 4 + 15) / 16 > 65535) return -1;
-  if (KW == 3) return launch_dw_s1<3, T, 2>(a, st);
-  if (KW == 5) return launch_dw_s1<5, T, 2>(a, st);
-  return -1;
+  return KW == 3 ? launch_dw_s1<3, T, 2>(a, st) : launch_dw_s1<5, T, 2>(a, st);
 }
 
 // Stride-2 input gradient, same tiling: dx[y][x] = sum over (ky, kx) with (y + pt - ky) and (x + pl - kx) even of
@@ -272,27 +288,22 @@ __global__ __launch_bounds__(256) void dw_dgrad_s2_kernel(const DwS1Args<T> a) {
     if (x0 + j < a.DW_) st4(orow + (size_t)(x0 + j) * a.ldd, acc[j]);
 }
 template <typename T>
-int dw_s2_dgrad_dispatch(const DwS1Args<T>& a, int KW, hipStream_t st) {
-  if ((long long)a.N * a.DH > 65535 || (a.C / 4 + 15) / 16 > 65535) return -1;
+int dw_s2_dgrad_dispatch(const DwS1Args<T>& a, int KW, bool odd, hipStream_t st) {        // dw_route: KW is 3 or 5
   const dim3 grid((unsigned)((a.DW_ + 16 * DW_XT - 1) / (16 * DW_XT)), (unsigned)(a.N * a.DH), (unsigned)((a.C / 4 + 15) / 16));
   const size_t lds = (size_t)a.KH * KW * 64 * sizeof(float);
-  const bool odd = (a.pl & 1) != 0;
   if (KW == 3) { if (odd) hipLaunchKernelGGL((dw_dgrad_s2_kernel<3, T, 1>), grid, dim3(256), lds, st, a); else hipLaunchKernelGGL((dw_dgrad_s2_kernel<3, T, 0>), grid, dim3(256), lds, st, a); }
-  else if (KW == 5) { if (odd) hipLaunchKernelGGL((dw_dgrad_s2_kernel<5, T, 1>), grid, dim3(256), lds, st, a); else hipLaunchKernelGGL((dw_dgrad_s2_kernel<5, T, 0>), grid, dim3(256), lds, st, a); }
-  else return -1;
+  else { if (odd) hipLaunchKernelGGL((dw_dgrad_s2_kernel<5, T, 1>), grid, dim3(256), lds, st, a); else hipLaunchKernelGGL((dw_dgrad_s2_kernel<5, T, 0>), grid, dim3(256), lds, st, a); }
   SSG_LAUNCH_CHECK();
   return SSG_OK;
 }
-// returns -1 if the shape is not covered (caller falls back to the generic kernel)
+// stride-1 forward, and input gradient with a.flip (dw_route: KW is 3, 5, 7 or 9)
 template <typename T>
 int dw_s1_dispatch(const DwS1Args<T>& a, int KW, hipStream_t st) {
-  if ((long long)a.N * a.DH > 65535 || (a.C / 4 + 15) / 16 > 65535) return -1;     // grid.y / grid.z limits
   switch (KW) {
     case 3: return launch_dw_s1<3, T>(a, st);
     case 5: return launch_dw_s1<5, T>(a, st);
     case 7: return launch_dw_s1<7, T>(a, st);
-    case 9: return launch_dw_s1<9, T>(a, st);
-    default: return -1;
+    default: return launch_dw_s1<9, T>(a, st);
   }
 }
 
@@ -520,15 +531,10 @@ int dwconv_fwd_impl(const T* in, int N, int H, int W, int C, int ld, const float
   int rc = dw_check("dwconv_fwd", in, N, H, W, C, ld, KH, KW, stride);
   if (rc) return rc;
   SSG_REQUIRE(w && out && OH > 0 && OW > 0 && ldo % 4 == 0, SSG_EINVAL, "dwconv_fwd: bad output");
-  if (stride == 1 && ssg_aligned16(in) && ssg_aligned16(out)) {
-    const DwS1Args<T> s1{in, w, bias, out, N, H, W, OH, OW, C, ld, ldo, KH, pad_top, pad_left, 0};
-    rc = dw_s1_dispatch<T>(s1, KW, (hipStream_t)stream);
-    if (rc >= 0) return rc;
-  }
-  if (stride == 2 && KH == KW && ssg_aligned16(in) && ssg_aligned16(out)) {
-    const DwS1Args<T> s2{in, w, bias, out, N, H, W, OH, OW, C, ld, ldo, KH, pad_top, pad_left, 0};
-    rc = dw_s2_fwd_dispatch<T>(s2, KW, (hipStream_t)stream);
-    if (rc >= 0) return rc;
+  const int id = dw_route(DW_OP_FWD, stride, KH, KW, pad_left, (long long)N * OH, C, ssg_aligned16(in) && ssg_aligned16(out));
+  if (id != DW_FWD_GENERIC) {
+    const DwS1Args<T> t{in, w, bias, out, N, H, W, OH, OW, C, ld, ldo, KH, pad_top, pad_left, 0};
+    return id == DW_FWD_S1 ? dw_s1_dispatch<T>(t, KW, (hipStream_t)stream) : dw_s2_fwd_dispatch<T>(t, KW, (hipStream_t)stream);
   }
   DwArgs<T> a{in, w, bias, nullptr, out, N, H, W, C, ld, KH, KW, stride, pad_top, pad_left, OH, OW, ldo};
   hipLaunchKernelGGL(dw_fwd_kernel<T>, dim3(elem_grid((long long)N * OH * OW * (C / 4))), dim3(256), 0, (hipStream_t)stream, a);
@@ -542,16 +548,15 @@ int dwconv_dgrad_impl(const T* dout, int lddo, int N, int H, int W, int C, const
   int rc = dw_check("dwconv_dgrad", dout, N, OH, OW, C, lddo, KH, KW, stride);
   if (rc) return rc;
   SSG_REQUIRE(w && dx && H > 0 && W > 0 && lddx % 4 == 0, SSG_EINVAL, "dwconv_dgrad: bad output");
-  if (stride == 1 && ssg_aligned16(dout) && ssg_aligned16(dx)) {
+  const int id = dw_route(DW_OP_DGRAD, stride, KH, KW, pad_left, (long long)N * H, C, ssg_aligned16(dout) && ssg_aligned16(dx));
+  if (id == DW_DGRAD_S1_FLIP) {
     // dx = correlation of dout with the flipped kernel, pads K-1-pad
     const DwS1Args<T> s1{dout, w, nullptr, dx, N, OH, OW, H, W, C, lddo, lddx, KH, KH - 1 - pad_top, KW - 1 - pad_left, 1};
-    rc = dw_s1_dispatch<T>(s1, KW, (hipStream_t)stream);
-    if (rc >= 0) return rc;
+    return dw_s1_dispatch<T>(s1, KW, (hipStream_t)stream);
   }
-  if (stride == 2 && KH == KW && ssg_aligned16(dout) && ssg_aligned16(dx)) {
+  if (id != DW_DGRAD_GENERIC) {
     const DwS1Args<T> s2{dout, w, nullptr, dx, N, OH, OW, H, W, C, lddo, lddx, KH, pad_top, pad_left, 0};
-    rc = dw_s2_dgrad_dispatch<T>(s2, KW, (hipStream_t)stream);
-    if (rc >= 0) return rc;
+    return dw_s2_dgrad_dispatch<T>(s2, KW, id == DW_DGRAD_S2_ODD, (hipStream_t)stream);
   }
   DwArgs<T> a{nullptr, w, nullptr, dout, dx, N, H, W, C, lddx, KH, KW, stride, pad_top, pad_left, OH, OW, lddo};
   hipLaunchKernelGGL(dw_dgrad_kernel<T>, dim3(elem_grid((long long)N * H * W * (C / 4))), dim3(256), 0, (hipStream_t)stream, a);
@@ -565,7 +570,7 @@ int dwconv_wgrad_impl(const T* in, int N, int H, int W, int C, int ld, const T* 
   int rc = dw_check("dwconv_wgrad", in, N, H, W, C, ld, KH, KW, stride);
   if (rc) return rc;
   SSG_REQUIRE(dout && dw && ws && OH > 0 && OW > 0, SSG_EINVAL, "dwconv_wgrad: bad args");
-  const bool tiled = (stride == 1 && (KW == 3 || KW == 5 || KW == 7 || KW == 9)) || (stride == 2 && (KW == 3 || KW == 5));
+  const bool tiled = dw_route(DW_OP_WGRAD, stride, KH, KW, pad_left, 0, C, true) != DW_WGRAD_GENERIC;
   // work units: pixels, or x-quads of 4 consecutive output pixels for the tiled kernels; the partial buffer is sized for the
   // pixel count (ssg_dwconv2d_wgrad_workspace_bytes), which bounds both
   const long long P = tiled ? (long long)N * OH * ((OW + 3) / 4) : (long long)N * OH * OW;
@@ -606,6 +611,10 @@ extern "C" int ssg_dwconv2d_dgrad_f32(const float* dout, int lddo, int N, int H,
 extern "C" int ssg_dwconv2d_dgrad_bf16(const void* dout, int lddo, int N, int H, int W, int C, const float* w, int KH, int KW, int stride,
                                        int pad_top, int pad_left, int OH, int OW, void* dx, int lddx, void* stream) {
   return dwconv_dgrad_impl<ssg_bf16>((const ssg_bf16*)dout, lddo, N, H, W, C, w, KH, KW, stride, pad_top, pad_left, OH, OW, (ssg_bf16*)dx, lddx, stream);
+}
+
+extern "C" int ssg_dwconv2d_kernel_id(int op, int stride, int KH, int KW, int pad_left, int64_t NDH, int C, int aligned16) {
+  return dw_route(op, stride, KH, KW, pad_left, (long long)NDH, C, aligned16 != 0);
 }
 
 extern "C" int64_t ssg_dwconv2d_wgrad_workspace_bytes(int N, int OH, int OW, int C, int KH, int KW) {
