@@ -120,6 +120,28 @@ int ssg_conv_set_k32_mode(int mode);
 int64_t ssg_pack_weights_split_bytes(int R, int Kp, int BN);
 int ssg_pack_weights_split_bf16x3(const float* w_packed, int R, int Kp, int BN, void* out, void* stream);
 
+/* Opt-in bf16 INFERENCE convolution (conv_halo_k32_x1.hip): the 3x3 stride-1 pad-1 forward conv of an eval-mode BasicBlock
+ * (archs.py:210,212 under model.eval(), api.py:376-390) with both operands rounded ONCE to bf16 (round to nearest even) and one
+ * v_mfma_f32_16x16x32_bf16 per product, fp32 accumulation, fp32 tensors in HBM.  An APPROXIMATION: |error| <= (2^-8 + 2^-18) *
+ * conv(|x|, |w|) from the operand rounding, plus fp32 accumulation.  Never selected by ssg_conv2d_f32; no mode, no environment
+ * variable: the caller launches it by name.  Non-finite results are those of the fp32 kernels (a tile that meets one is recomputed
+ * in fp32: an fp32 value above ~3.39e38 rounds to bf16 infinity).
+ * ssg_conv2d_bf16x1_ok: 0, or the pack format code (1128 / 1064 = 8 x 32-pixel x 128- / 64-channel tiles) the launch for `d`
+ * reads.  Legal: the nine taps of a 3x3 window, kmode 0, unit strides, out_oy = out_ox = 0, C1 % 32 == 0, C2 % 32 == 0,
+ * Cout % 64 == 0, GW >= 17, 16-byte aligned in1 / in2 / w / bias / res / out with ld % 4 == 0, inputs below 4 GiB, act none /
+ * ReLU / leaky ReLU, and bnpart, ws, parity_merge, in_scale, bwd_x unset (w_split is not read).  d->w stays the fp32 packed
+ * matrix (the non-finite path reads it).
+ * ssg_pack_weights_bf16x1(d->w rows [R][Kp] in kmode 0, R, Kp, BN = that code): ssg_pack_weights_bf16x1_bytes bytes, layout
+ * [R/bn][Kp/32 steps = chunk32 * 9 + tap][bn/16 fragments][64 lanes][16 B] (bn = BN - 1000; R % bn == 0, Kp % 288 == 0) -- the
+ * 1128 / 1064 layout of ssg_pack_weights_split_bf16x3 with one plane, a third of its bytes.
+ * ssg_conv2d_bf16x1_f32 validates on the host and returns a status before any launch.
+ * ssg_conv2d_bf16x1_kernel_id: 70 / 71 = conv_halo_k32_x1_kernel<128> / <64> (profiling labels), SSG_EINVAL where refused. */
+int ssg_conv2d_bf16x1_ok(const ssg_conv_desc* d);
+int ssg_conv2d_bf16x1_kernel_id(const ssg_conv_desc* d);
+int ssg_conv2d_bf16x1_f32(const ssg_conv_desc* d, const void* w_bf16x1, void* stream);
+int64_t ssg_pack_weights_bf16x1_bytes(int R, int Kp, int BN);
+int ssg_pack_weights_bf16x1(const float* w_packed, int R, int Kp, int BN, void* out, void* stream);
+
 /* Launches whose pixel-tile count leaves most of the chip idle (the 16x16 / 32x32 levels of archs.py:583-589, the
  * Cout <= 64 input gradients of SPADE's gamma|beta conv normalization.py:94-96, batch-1 inference api.py:322) split the
  * reduction over 16-channel chunks into slabs; an ordered second stage adds the slabs and applies bias / res / act

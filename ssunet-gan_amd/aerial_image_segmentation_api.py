@@ -58,11 +58,11 @@ _GRAPHS = {}
 
 
 def _cached_operands(model):
-    """Every tensor the packed-weight (`ops._pack`, `bf16._pack`), BN-fold (`BasicBlock._folded`) and gamma|beta-concat
+    """Every tensor the packed-weight (`ops._pack`, `ops._x1_pack`, `bf16._pack`), BN-fold (`BasicBlock._folded`) and gamma|beta-concat
     (`blocks._spade_cat`) caches of `model` hold right now."""
     held = []
     for t in list(model.parameters()) + list(model.buffers()):
-        for name in ('_ssg_pack', '_ssg_pack_bf16'):
+        for name in ('_ssg_pack', '_ssg_pack_bf16', '_ssg_pack_bf16x1'):
             c = t.__dict__.get(name)
             if c is not None:
                 held += list(c[1].values())
@@ -74,16 +74,18 @@ def _cached_operands(model):
         if c is not None:
             held += list(c[1])
             for t in c[1]:                       # the folded weights are themselves packed per use
-                p = t.__dict__.get('_ssg_pack')
-                if p is not None:
-                    held += list(p[1].values())
+                for name in ('_ssg_pack', '_ssg_pack_bf16x1'):
+                    p = t.__dict__.get(name)
+                    if p is not None:
+                        held += list(p[1].values())
     return held
 
 
-def _graph_for(model, shape, device):
+def _graph_for(model, shape, device, precision='fp32'):
     """hipGraph of `sigmoid(model(x))` for one input shape (eval mode), captured after a warm-up call that fills the
     packed-weight and BN-fold caches; tied to the parameter values it was captured with (keyed by the weight / statistics
-    epochs).  MEASURED (profiles/r02_a_bench_extra.jsonl): one 3x512x512 patch takes 6.52 ms launched kernel by kernel and
+    epochs) and to the `precision` it was captured under (`ops.infer_precision`: an fp32 capture is never replayed for a
+    bf16x1 request, nor the other way round).  MEASURED (profiles/r02_a_bench_extra.jsonl): one 3x512x512 patch takes 6.52 ms launched kernel by kernel and
     6.48 ms as a graph replay -- the ~330 launches of a batch-1 forward are NOT what limits the patch rate (round 1 assumed
     so); the deep levels do (16x16 x 768 channels at batch 1 is 12 workgroups of 432 K-steps on a 256-CU chip).  The graph
     path is therefore opt-in (`graph=True`), kept because it takes the Python launch path off the host for callers that
@@ -93,7 +95,7 @@ def _graph_for(model, shape, device):
     # stamp with -- plus the two epochs that cover raw-pointer writes.  load_state_dict() / any in-place edit changes a version
     # and forces a new capture instead of replaying the old weights.
     stamp = tuple((t.data_ptr(), t._version) for t in list(model.parameters()) + list(model.buffers()))
-    key = (id(model), tuple(shape), str(device), ops._WEIGHT_EPOCH[0], ops._STATS_EPOCH[0], hash(stamp))
+    key = (id(model), tuple(shape), str(device), ops._WEIGHT_EPOCH[0], ops._STATS_EPOCH[0], hash(stamp), precision)
     hit = _GRAPHS.get(key)
     if hit is not None and hit[0]() is model and hit[4] == stamp:
         return hit[1:4]
@@ -101,13 +103,13 @@ def _graph_for(model, shape, device):
     static_in = torch.zeros(shape, dtype=torch.float32, device=device)
     side = torch.cuda.Stream(device=device)
     side.wait_stream(torch.cuda.current_stream(device))
-    with torch.cuda.stream(side):                       # warm-up on the capture stream: caches, lazy kernel attributes
+    with torch.cuda.stream(side), ops.infer_precision(precision):   # warm-up on the capture stream: caches, lazy kernel attributes
         ops.sigmoid(model(static_in))
     torch.cuda.current_stream(device).wait_stream(side)
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    with ops.infer_precision(precision), torch.cuda.graph(graph):
         static_out = ops.sigmoid(model(static_in))
-    for k in [k for k, v in _GRAPHS.items() if v[0]() is None or (k[0] == id(model) and k[1] == tuple(shape))]:
+    for k in [k for k, v in _GRAPHS.items() if v[0]() is None or (k[0] == id(model) and k[1] == tuple(shape) and k[-1] == precision)]:
         del _GRAPHS[k]                                  # stale captures of this model / dead models
     # keep what the captured kernels read alive for as long as the capture: a later eager forward with other weights
     # re-fills the caches and would otherwise free these tensors under the graph
@@ -115,18 +117,23 @@ def _graph_for(model, shape, device):
     return graph, static_in, static_out
 
 
-def infer_patches(model, img_patch_set, batch_size=16, graph=False):
+def infer_patches(model, img_patch_set, batch_size=16, graph=False, precision='fp32'):
     """sigmoid(model(patch)) for every patch, batched.  img_patch_set: [P, C, H, W] float32 (numpy or
     tensor, as `get_patched_input` builds it); returns a float32 tensor [P, num_classes, H, W] on the host.
-    `graph=True`: replay a captured hipGraph per batch instead of launching kernel by kernel (same values; see _graph_for)."""
+    `graph=True`: replay a captured hipGraph per batch instead of launching kernel by kernel (same values; see _graph_for).
+    `precision`: 'fp32' (default: today's kernels, bit for bit) or 'bf16x1' -- an APPROXIMATION that trades the fp32 guarantee for
+    speed: the 3x3 stride-1 convs of the model's eval-mode BasicBlocks whose shape the one-term kernel takes (32-channel multiples
+    in, 64 out, at least 17 pixels wide: not the stem's 3-channel conv, not the 16x16 levels) round x and the BN-folded weights
+    once to bf16 and accumulate in fp32 (`ops.conv2d_bf16x1`).  The 1x1 shortcuts, stride-2 convs, SPADE, pooling and resampling
+    layers and every tensor in memory stay fp32.  Any other string raises ValueError."""
     x = torch.as_tensor(img_patch_set, dtype=torch.float32)
     model.eval()
     outs = []
-    with torch.no_grad():
+    with torch.no_grad(), ops.infer_precision(precision):
         for i in range(0, x.shape[0], batch_size):
             xb = x[i:i + batch_size].cuda(non_blocking=True)
             if graph:
-                g, static_in, static_out = _graph_for(model, xb.shape, xb.device)
+                g, static_in, static_out = _graph_for(model, xb.shape, xb.device, precision)
                 static_in.copy_(xb)
                 g.replay()
                 y = static_out.clone()
@@ -275,7 +282,7 @@ def unique_origins(org):
     return list(count.keys()), list(count.values())
 
 
-def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_probs=False):
+def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_probs=False, precision='fp32'):
     """`segmentation_inference_full(model, *get_patched_input(...), config, False)[0]` for an image already in memory, with
     everything between the uint8 image and the uint8 masks on the device: the image is uploaded once, each batch of patches is
     cut, resized and normalised by `ops.sw_gather_patches`, `sigmoid(model(x))` stays on the device, `ops.sw_merge_masks` does
@@ -283,6 +290,8 @@ def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_pro
     `dedupe`: infer each distinct origin once and let it enter the merge with its multiplicity (the same masks whenever
     equal patches give equal probabilities, which they do inside one batch composition).
     `return_probs`: also return (the host copy [P, C, S, S] of the probabilities that were merged, their origins, their weights).
+    `precision`: 'fp32' (default, unchanged) or 'bf16x1', the approximation described at `infer_patches` (bf16 operand rounding in
+    the BasicBlock 3x3 stride-1 convs); masks can differ from the fp32 path where a probability is near the threshold.
     Not covered, as on the host path they stay with: the ground-truth branch, PNG decoding, non-square inference sizes and
     resize factors other than 1 and 2."""
     p_size, size, overlap, classes = config['patch_size'], config['input_w'], config['patch_overlap'], config['num_classes']
@@ -298,7 +307,7 @@ def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_pro
     img = torch.from_numpy(np.ascontiguousarray(img_bgr)).to(dev)
     probs = ops.new_nhwc(len(org), classes, size, size, dev)
     model.eval()
-    with torch.no_grad():
+    with torch.no_grad(), ops.infer_precision(precision):
         for i in range(0, len(org), batch_size):
             x = ops.sw_gather_patches(img, org[i:i + batch_size], p_size, size)
             ops.sigmoid_into(model(x), probs[i:i + batch_size])
@@ -336,11 +345,12 @@ def load_segmentation_models(config_file):
     return model, config
 
 
-def segmentation_inference_full(model, img_input, img_patch_set, mask_patch_set, config, gt_mask_flag, batch_size=12):
+def segmentation_inference_full(model, img_input, img_patch_set, mask_patch_set, config, gt_mask_flag, batch_size=12, precision='fp32'):
     """api.py:376-410 complete: (all_class_mask, gt_class_mask) as lists of uint8 {0, 255} masks at image resolution.  The model
-    forward is batched (`batch_size` patches per launch sequence; 1 = the reference's loop)."""
+    forward is batched (`batch_size` patches per launch sequence; 1 = the reference's loop).  `precision`: see `infer_patches`
+    ('bf16x1' is an approximation with bf16 operand rounding in the BasicBlock 3x3 stride-1 convs)."""
     patch_size, infer_size, p_overlap = config['patch_size'], config['input_w'], config['patch_overlap']
-    full_output = list(infer_patches(model, img_patch_set, batch_size).numpy())
+    full_output = list(infer_patches(model, img_patch_set, batch_size, precision=precision).numpy())
     all_class_mask = patch_merge(img_input, full_output, patch_size, config, p_overlap)
     if gt_mask_flag is True:
         gt_label = []

@@ -588,6 +588,154 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, x
     return (y, part) if bn_stats else y
 
 
+# ----------------------------------------------------------------------------- opt-in bf16 inference convolution
+# csrc/conv_halo_k32_x1.hip: the 3x3 stride-1 pad-1 forward conv with both operands rounded once to bf16 and one MFMA per product
+# (ssg_conv2d_bf16x1_f32).  An approximation, forward only, chosen per call: nothing here is reached from a training path, and
+# ops.conv2d never routes to it.
+_X1_LABELS = {70: 'conv_halo_k32_x1_kernel<128>', 71: 'conv_halo_k32_x1_kernel<64>'}
+_X1_TAPS = _taps_fwd(3, 3, 1)
+_INFER_PRECISIONS = ('fp32', 'bf16x1')
+_INFER_PRECISION = ['fp32']
+
+
+class infer_precision(object):
+    """with ops.infer_precision('bf16x1'): ...   -- eval-mode modules (archs.BasicBlock) run their 3x3 stride-1 convs on
+    conv2d_bf16x1 where conv2d_bf16x1_ok holds (bf16 operand rounding, fp32 accumulation: an approximation) and stay on conv2d
+    elsewhere.  'fp32' (the default) is today's behaviour.  Read by eval-mode module code only, never by a training path."""
+
+    def __init__(self, mode):
+        if mode not in _INFER_PRECISIONS:
+            raise ValueError('infer_precision: unknown mode %r (one of %s)' % (mode, ', '.join(_INFER_PRECISIONS)))
+        self.mode = mode
+
+    def __enter__(self):
+        self.prev = _INFER_PRECISION[0]; _INFER_PRECISION[0] = self.mode
+        return self
+
+    def __exit__(self, *a):
+        _INFER_PRECISION[0] = self.prev
+
+
+def infer_precision_mode():
+    """The mode the innermost `infer_precision` block set ('fp32' outside any)."""
+    return _INFER_PRECISION[0]
+
+
+def _x1_desc(x, x2, weight, res, out=None):
+    """ssg_conv_desc of conv2d_bf16x1 for these tensors.  Pointers the predicate does not dereference (the packed weights, an
+    output that does not exist yet, a tensor that to_nhwc would still copy) are stood in for by an aligned non-null value."""
+    def side(t):
+        ld = nhwc_ld(t)
+        return (t.data_ptr(), ld) if ld is not None else (16, pad4(t.shape[1]))
+    n, c1, h, w = x.shape
+    d = ConvDesc()
+    d.in1, d.ld1 = side(x); d.C1 = c1
+    if x2 is not None:
+        d.in2, d.ld2 = side(x2); d.C2 = x2.shape[1]
+    else:
+        d.in2 = None; d.C2 = 0; d.ld2 = 0
+    d.N, d.H, d.W = n, h, w
+    d.w = 16; d.Kp = 9 * (d.C1 + d.C2); d.kmode = 0
+    d.bias = None
+    if res is not None:
+        d.res, d.ldr = side(res)
+    else:
+        d.res = None; d.ldr = 0
+    d.Cout = weight.shape[0]
+    d.out, d.ldo = side(out) if out is not None else (16, pad4(d.Cout))
+    d.GH, d.GW, d.OH, d.OW = h, w, h, w
+    d.in_sy = d.in_sx = d.out_sy = d.out_sx = 1
+    d.out_oy = d.out_ox = 0
+    _fill_taps(d, _X1_TAPS)
+    d.act = ACT_NONE; d.slope = 0.0
+    d.bnpart = None; d.ws = None; d.ws_bytes = 0; d.w_split = None; d.parity_merge = 0
+    d.in_scale = None; d.in_shift = None; d.in_act = ACT_NONE; d.in_slope = 0.0
+    d.bwd_x = None; d.bwd_ldx = 0; d.bwd_scale = None; d.bwd_shift = None; d.bwd_mean = None; d.bwd_act = ACT_NONE; d.bwd_slope = 0.0
+    return d
+
+
+def _x1_shapes_ok(x, weight, x2, res):
+    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x.dtype != torch.float32 or weight.dtype != torch.float32:
+        return False
+    c2 = x2.shape[1] if x2 is not None else 0
+    if x.shape[1] + c2 != weight.shape[1] or (x2 is not None and (x2.dtype != torch.float32 or x2.shape[0] != x.shape[0] or x2.shape[2:] != x.shape[2:])):
+        return False
+    return res is None or (res.dtype == torch.float32 and tuple(res.shape) == (x.shape[0], weight.shape[0], x.shape[2], x.shape[3]))
+
+
+def conv2d_bf16x1_ok(x, weight, x2=None, res=None):
+    """True where conv2d_bf16x1 takes these tensors (ssg_conv2d_bf16x1_ok): a 3x3 weight, C1 % 32 == 0 and C2 % 32 == 0,
+    Cout % 64 == 0, W >= 17, fp32 tensors below 4 GiB.  Launches nothing."""
+    if not _x1_shapes_ok(x, weight, x2, res):
+        return False
+    return call('ssg_conv2d_bf16x1_ok', C.byref(_x1_desc(x, x2, weight, res))) != 0
+
+
+def _x1_pack(weight, wpk, kp, fmt):
+    """The bf16 pack of `weight` (OIHW) for format `fmt`, built from its fp32 kmode-0 matrix `wpk`; cached on the weight tensor as
+    `_ssg_pack_bf16x1`, stamped like `_ssg_pack`."""
+    stamp = (weight.data_ptr(), weight._version, _WEIGHT_EPOCH[0])
+    cache = weight.__dict__.get('_ssg_pack_bf16x1')
+    if cache is None or cache[0] != stamp:
+        cache = (stamp, {})
+        try:
+            weight._ssg_pack_bf16x1 = cache
+        except Exception:
+            pass
+    hit = cache[1].get(fmt)
+    if hit is None:
+        nbytes = call('ssg_pack_weights_bf16x1_bytes', weight.shape[0], kp, fmt)
+        hit = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
+        call('ssg_pack_weights_bf16x1', ptr(wpk), weight.shape[0], kp, fmt, ptr(hit), stream_ptr())
+        cache[1][fmt] = hit
+    return hit
+
+
+def _conv_bf16x1_impl(x, weight, bias, act, slope, x2=None, res=None, out=None):
+    """conv2d_bf16x1 after its argument checks; `out`: an NHWC destination (a channel slice of a wider buffer in the layout tests)."""
+    x = to_nhwc(x.detach())
+    x2 = to_nhwc(x2.detach()) if x2 is not None else None
+    res = to_nhwc(res.detach()) if res is not None else None
+    n, c1, h, w = x.shape
+    o = weight.shape[0]
+    wpk, kp, kmode = _pack(weight, 0, _X1_TAPS, weight.shape[1], c1)
+    if out is None:
+        out = new_nhwc(n, o, h, w, x.device)
+    d = _x1_desc(x, x2, weight, res, out)
+    d.w = wpk.data_ptr(); d.Kp = kp; d.kmode = kmode
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.act = int(act); d.slope = float(slope)
+    fmt = call('ssg_conv2d_bf16x1_ok', C.byref(d))
+    if not fmt:
+        call('ssg_conv2d_bf16x1_f32', C.byref(d), None, stream_ptr())      # refused on the host, nothing launched: raises with the reason
+    pack = _x1_pack(weight, wpk, kp, fmt)
+    label = None
+    if PROFILE is not None:
+        label = _X1_LABELS.get(call('ssg_conv2d_bf16x1_kernel_id', C.byref(d)), '?')
+        if PROFILE_SHAPES:
+            label += ' n%d %dx%d cin%d cout%d taps9 s1/1' % (n, h, w, weight.shape[1], o)
+    with _Timed(label, 2.0 * n * h * w * o * weight.shape[1] * 9, _ROLE[0]):
+        call('ssg_conv2d_bf16x1_f32', C.byref(d), ptr(pack), stream_ptr())
+    return out
+
+
+def conv2d_bf16x1(x, weight, bias=None, act=ACT_NONE, slope=0.0, x2=None, res=None):
+    """act(conv3x3(cat(x, x2), weight, stride 1, padding 1) + bias + res) with x, x2 and weight rounded once to bf16 (round to
+    nearest even) and fp32 accumulation: one sixth of the matrix instructions of the fp32-class kernel behind `conv2d`.
+    An APPROXIMATION, |error| <= (2^-8 + 2^-18) * conv(|x|, |w|); bias, res and the output are fp32.  Inference only: raises
+    RuntimeError when autograd is recording and an argument requires grad, ValueError where `conv2d_bf16x1_ok` says no, and there
+    is no CPU fallback."""
+    for t in (x, weight, bias, x2, res):
+        if t is not None:
+            _lib.require_gpu(t)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias, x2, res)):
+        raise RuntimeError('conv2d_bf16x1 is inference-only (no backward): call it under torch.no_grad() or on tensors that do not require grad')
+    if not conv2d_bf16x1_ok(x, weight, x2=x2, res=res):
+        raise ValueError('conv2d_bf16x1: no bf16x1 kernel for x %s x2 %s weight %s res %s (conv2d_bf16x1_ok is False)' % (
+            tuple(x.shape), None if x2 is None else tuple(x2.shape), tuple(weight.shape), None if res is None else tuple(res.shape)))
+    return _conv_bf16x1_impl(x, weight, bias, act, slope, x2=x2, res=res)
+
+
 # ----------------------------------------------------------------------------- linear (as 1x1 conv over a 1 x N "image")
 class _Linear(torch.autograd.Function):
     @staticmethod

@@ -53,9 +53,22 @@ def sliding_window_rows(G):
     t_host = timed(host_path, 1, 2)
     t_dev = timed(lambda: A.segment_image(G, img, cfg, batch_size=12, dedupe=False), 1, 3)
     t_dedupe = timed(lambda: A.segment_image(G, img, cfg, batch_size=12, dedupe=True), 1, 3)
+    # the opt-in bf16x1 precision (ops.infer_precision: an approximation), same image and geometry, alternated with the fp32 rows
+    t_dev_x1 = timed(lambda: A.segment_image(G, img, cfg, batch_size=12, dedupe=False, precision='bf16x1'), 1, 3)
+    t_dedupe_x1 = timed(lambda: A.segment_image(G, img, cfg, batch_size=12, dedupe=True, precision='bf16x1'), 1, 3)
+    t_dev2 = timed(lambda: A.segment_image(G, img, cfg, batch_size=12, dedupe=False), 1, 3)
+    t_dedupe2 = timed(lambda: A.segment_image(G, img, cfg, batch_size=12, dedupe=True), 1, 3)
+    m32 = A.segment_image(G, img, cfg, batch_size=12, dedupe=True)
+    mx1 = A.segment_image(G, img, cfg, batch_size=12, dedupe=True, precision='bf16x1')
+    differ = float(np.mean([np.mean(a != b) for a, b in zip(m32, mx1)]))
     out = [{'what': 'C5 one 2048^2 uint8 image -> 3 class masks, patch 1024 / overlap 0.5 / inference 512^2, batch 12, from the in-memory array',
             's_per_image_host_gather_and_merge': round(t_host, 3), 's_per_image_segment_image': round(t_dev, 4),
-            's_per_image_segment_image_dedupe': round(t_dedupe, 4)}]
+            's_per_image_segment_image_dedupe': round(t_dedupe, 4)},
+           {'what': "C5 the same image with precision='bf16x1' (bf16 operand rounding in the BasicBlock 3x3 stride-1 convs; seeded, untrained model), "
+                    'fp32 rows repeated after it in the same process',
+            's_per_image_segment_image_bf16x1': round(t_dev_x1, 4), 's_per_image_segment_image_dedupe_bf16x1': round(t_dedupe_x1, 4),
+            's_per_image_segment_image_fp32_again': round(t_dev2, 4), 's_per_image_segment_image_dedupe_fp32_again': round(t_dedupe2, 4),
+            'fraction_of_mask_bytes_that_differ_from_fp32': round(differ, 6)}]
     # the two kernels alone (HIP events), for all 36 patches and for the 9 distinct ones, against the forwards they surround
     dimg = torch.from_numpy(img).to(dev)
     org36 = A.patch_origins(2048, 2048, 1024, 0.5)
@@ -83,6 +96,22 @@ def sliding_window_rows(G):
             with torch.no_grad():
                 dt = timed(lambda: [ops.sigmoid(G(x[i:i + 12])) for i in range(0, 36, 12)], 1, 3)
             row['ms_36_forwards_batch_12'] = round(dt * 1e3, 2)
+            with torch.no_grad(), ops.infer_precision('bf16x1'):
+                dt = timed(lambda: [ops.sigmoid(G(x[i:i + 12])) for i in range(0, 36, 12)], 1, 3)
+            row['ms_36_forwards_batch_12_bf16x1'] = round(dt * 1e3, 2)
+            # where an eval forward's time goes under each precision: HIP-event time of the conv launches by kernel label
+            for prec in ('fp32', 'bf16x1'):
+                ops.PROFILE = []
+                try:
+                    with torch.no_grad(), ops.infer_precision(prec):
+                        ops.sigmoid(G(x[:12]))
+                    torch.cuda.synchronize()
+                    by = {}
+                    for rec in ops.PROFILE:
+                        by[rec[0]] = by.get(rec[0], 0.0) + rec[2].elapsed_time(rec[3])
+                finally:
+                    ops.PROFILE = None
+                row['ms_conv_launches_one_batch_12_forward_%s' % prec] = {k: round(v, 3) for k, v in sorted(by.items(), key=lambda kv: -kv[1])[:8]}
         del x, probs
     out.append(row)
     return out
