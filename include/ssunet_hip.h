@@ -360,6 +360,26 @@ int ssg_bn_bwd_apply_f32(const float* x, const float* y, const float* dy, int64_
                          float* dx, int lddx, float* dres, int lddres,
                          float* dweight, float* dbias, void* stream);
 /* eval-mode / generic per-channel affine: y = x*scale + shift -> act (also used for bias+act) */
+/* Backward of a batch norm whose statistics are CONSTANTS (eval mode / frozen: torch.nn.functional.batch_norm(training=False),
+ * archs.py:211,213 under model.eval()), in one pass -- no per-batch mean to subtract, so the stores ride the reduction sweep:
+ *   g = dy * act'(.)   mask from the saved output y, or -- y = NULL, forward without residual -- recomputed as
+ *                      x*scale + shift with the forward's own fma (ReLU / LeakyReLU); swish: derivative at x*scale + shift
+ *   dx   = g * scale[c]         (scale = NULL: dx = g;  dx = NULL: not written)
+ *   dres = g                    (dres = NULL: not written)
+ *   sums[0:C] = sum_p g,  sums[C:2C] = sum_p g * (x - mean[c]) * invstd[c]   (mean = invstd = NULL: second half written as 0, x may be NULL)
+ * fp64 partial rows, fixed order, no atomics: sums carry the bits of ssg_bn_bwd_reduce_f32 on the same inputs.
+ * ws: ssg_bn_workspace_bytes(P, C) bytes.  C % 4 == 0; every row stride is its own (channel slices, pad lanes).
+ * With x = mean = scale = NULL: activation backward + bias gradient of a conv epilogue in one read of dy. */
+int ssg_bn_frozen_bwd_f32(const float* x, const float* y, const float* dy, int64_t P, int C, int ldx, int ldy, int lddy,
+                          const float* mean, const float* invstd, const float* scale, const float* shift, int act, float slope,
+                          float* dx, int lddx, float* dres, int lddres, double* sums, void* ws, void* stream);
+/* Gradients through the fold of a frozen batch norm into its conv: Wf[o] = W[o]*s[o], bf[o] = beta[o] - mean[o]*s[o], s = gamma*invstd.
+ * Per output channel o, K = Cin*kh*kw:  t = sum_k dwf[o,k]*w[o,k] (fp64, fixed order)
+ *   dw[o,k] = dwf[o,k]*s[o];   dgamma[o] = (t - mean[o]*sums_g[o]) * invstd[o];   dbeta[o] = sums_g[o]     (each stored once, from fp64)
+ * sums_g = sum_p of the gradient at the conv output (ssg_bn_frozen_bwd_f32's sums[0:C]).  dw may be NULL, and so may the pair
+ * dgamma / dbeta (w, mean, invstd, sums_g are then not read). */
+int ssg_bn_fold_bwd_f32(const float* dwf, const float* w, int Cout, int64_t K, const float* s, const float* mean,
+                        const float* invstd, const double* sums_g, float* dw, float* dgamma, float* dbeta, void* stream);
 
 /* ------------------------------------------------------------------ pool / unpool / upsample
  * MaxPool2d(2,2,return_indices) archs.py:571,628-643; MaxUnpool2d(2,2) archs.py:572,648-659;

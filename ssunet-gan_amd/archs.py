@@ -9,7 +9,7 @@ import torch.nn as nn
 from torch.nn import init
 
 from . import ops
-from .blocks import basic_block
+from .blocks import basic_block, frozen_basic_block
 from .normalization import SPADE
 from ._lib import ACT_NONE, ACT_RELU
 
@@ -40,8 +40,23 @@ class BasicBlock(nn.Module):
         """`x2` (optional) is a second tensor concatenated after `x` along channels: the
         decoder's torch.cat([enc, up], 1) (archs.py:651-667) without materialising it."""
         sc = self.shortcut[0] if len(self.shortcut) else None
-        if self.training:
+        route = self._route()
+        if route == 'train':
             return basic_block(x, x2, self.conv1, self.bn1, self.conv2, self.bn2, sc, group=_sync_group(self.bn1))
+        if route == 'frozen':
+            # both batch norms on their running statistics with autograd recording (fine-tuning with frozen BN, or any gradient
+            # through an eval-mode model): the eval branch's three launches as ONE autograd node, always the fp32-class kernels
+            return frozen_basic_block(x, x2, self.conv1, self.bn1, self.conv2, self.bn2, sc, self._folded(), self._fold_consts())
+        if route == 'mixed':
+            # one batch norm frozen, or a non-affine one: the unfused composition, each ops.batch_norm_act honouring its own bn.training
+            s = self.conv1.stride[0]
+            y = ops.conv2d(x, self.conv1.weight, None, s, 1, x2=x2)
+            y = ops.batch_norm_act(y, self.bn1, act=ACT_RELU, group=_sync_group(self.bn1))
+            y = ops.conv2d(y, self.conv2.weight, None, 1, 1)
+            if sc is None and x2 is not None:
+                raise ValueError('identity shortcut with a two-tensor input')
+            r = ops.conv2d(x, sc.weight, None, s, 0, x2=x2) if sc is not None else x
+            return ops.batch_norm_act(y, self.bn2, res=r, act=ACT_RELU, group=_sync_group(self.bn2))
         # eval mode: the running-stat batch norms are folded into the conv weights, so the block is three
         # MFMA launches with bias / residual / ReLU epilogues and no batch-norm pass (sliding-window
         # inference, aerial_image_segmentation_api.py:376-390)
@@ -59,6 +74,36 @@ class BasicBlock(nn.Module):
         if x1 and ops.conv2d_bf16x1_ok(y, w2, res=r):
             return ops.conv2d_bf16x1(y, w2, b2, act=ACT_RELU, res=r)
         return ops.conv2d(y, w2, b2, 1, 1, act=ACT_RELU, res=r)
+
+    def _route(self):
+        """Which schedule forward() takes: 'train' (fused node on batch statistics), 'cached_eval' (folded weights under no_grad,
+        the inference path), 'frozen' (folded weights as one autograd node) or 'mixed' (unfused composition)."""
+        def batch(bn):
+            return bn.training or not bn.track_running_stats
+        if self.training and batch(self.bn1) and batch(self.bn2):
+            return 'train'
+        if not self.training and not torch.is_grad_enabled():
+            return 'cached_eval'
+        # (the frozen node's one-pass backward runs whole channel quads: other widths take the composition, whose batch norm pads its lanes)
+        if all(not batch(bn) and bn.weight is not None and bn.bias is not None and bn.num_features % 4 == 0 for bn in (self.bn1, self.bn2)):
+            return 'frozen'
+        return 'mixed'
+
+    def _fold_consts(self):
+        """((s, mean, invstd) of bn1, the same of bn2) with s = gamma * invstd as _folded() forms it: what the frozen node's
+        backward needs to carry gradients through the fold; cached like the folded weights."""
+        srcs = (self.bn1.weight, self.bn1.running_mean, self.bn1.running_var, self.bn2.weight, self.bn2.running_mean, self.bn2.running_var)
+        stamp = tuple((t.data_ptr(), t._version) for t in srcs) + (ops._WEIGHT_EPOCH[0], ops._STATS_EPOCH[0])
+        hit = getattr(self, '_fold_consts_cache', None)
+        if hit is not None and hit[0] == stamp:
+            return hit[1]
+        with torch.no_grad():
+            out = []
+            for bn in (self.bn1, self.bn2):
+                invstd = torch.rsqrt(bn.running_var + bn.eps)
+                out.append(((bn.weight * invstd).contiguous(), bn.running_mean.detach().clone(), invstd))
+        self._fold_consts_cache = (stamp, tuple(out))
+        return self._fold_consts_cache[1]
 
     def _folded(self):
         """(w1', b1', w2', b2') with w' = w * gamma/sqrt(var+eps), b' = beta - mean*gamma/sqrt(var+eps);

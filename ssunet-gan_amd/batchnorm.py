@@ -9,13 +9,16 @@ over RCCL between the two kernel stages of the batch norm, every rank evaluates
 `_compute_mean_std` (batchnorm.py:115-127: mean = sum/n, biased var, inv_std = clamp(var, eps)^-1/2,
 running_var from the unbiased var) itself, and backward all-reduces [sum g, sum g*xhat] the same way.
 """
+import functools
+
 import torch.nn as nn
 
 from . import dp, ops
 from ._lib import ACT_NONE
 
 __all__ = ['SynchronizedBatchNorm1d', 'SynchronizedBatchNorm2d', 'SynchronizedBatchNorm3d', 'convert_model',
-           'patch_sync_batchnorm', 'DataParallelWithCallback', 'patch_replication_callback']
+           'patch_sync_batchnorm', 'DataParallelWithCallback', 'patch_replication_callback', 'freeze_batch_norm',
+           'unfreeze_batch_norm']
 
 
 class _SynchronizedBatchNorm(nn.modules.batchnorm._BatchNorm):
@@ -70,6 +73,56 @@ def convert_model(module):
 def patch_sync_batchnorm(module, group=None):
     """In-place alternative to convert_model: keep the modules, mark them synchronized."""
     return dp.convert_sync_batchnorm(module, group)
+
+
+def _frozen_train(self, mode=True):
+    """nn.Module.train of a frozen batch norm: the children follow `mode`, the layer itself stays in eval mode."""
+    nn.Module.train(self, mode)
+    self.training = False
+    return self
+
+
+def freeze_batch_norm(module, freeze_affine=False):
+    """Fine-tuning with frozen batch-norm statistics: every _BatchNorm under `module` goes to eval mode and STAYS there through
+    later `module.train()` calls (both trainers call .train() every epoch).  Such a layer normalises with its running estimates,
+    writes none of them (num_batches_tracked included), issues no sync-BN collective, and stays differentiable in its input and in
+    gamma / beta.  `freeze_affine=True` also sets requires_grad_(False) on gamma / beta.  Returns the number of layers frozen."""
+    n = 0
+    for m in module.modules():
+        if isinstance(m, nn.modules.batchnorm._BatchNorm):
+            if '_ssg_frozen' not in m.__dict__:
+                m.__dict__['_ssg_frozen'] = tuple(p.requires_grad for p in (m.weight, m.bias) if p is not None)
+                # a partial of a module-level function: deepcopy and pickle (torch.save(model), spawn) carry it along
+                m.train = functools.partial(_frozen_train, m)
+            m.training = False
+            if freeze_affine:
+                for p in (m.weight, m.bias):
+                    if p is not None:
+                        p.requires_grad_(False)
+            n += 1
+    return n
+
+
+def unfreeze_batch_norm(module):
+    """Undo freeze_batch_norm: the layers follow .train() / .eval() again (each takes the mode of its parent now) and gamma / beta
+    get back the requires_grad they had.  Returns the number of layers released."""
+    n = 0
+    if isinstance(module, nn.modules.batchnorm._BatchNorm) and '_ssg_frozen' in module.__dict__:
+        n += _release(module, module.training)              # no parent to follow: it keeps its mode until the next .train()
+    for parent in module.modules():
+        for m in parent.children():
+            if isinstance(m, nn.modules.batchnorm._BatchNorm) and '_ssg_frozen' in m.__dict__:
+                n += _release(m, parent.training)
+    return n
+
+
+def _release(m, mode):
+    was = m.__dict__.pop('_ssg_frozen')
+    m.__dict__.pop('train', None)
+    for p, rg in zip([p for p in (m.weight, m.bias) if p is not None], was):
+        p.requires_grad_(rg)
+    m.training = mode
+    return 1
 
 
 class DataParallelWithCallback(nn.Module):

@@ -111,6 +111,94 @@ def basic_block(x1, x2, conv1, bn1, conv2, bn2, shortcut_conv, group=None):
                                int(conv1.stride[0]), var_mode, group)
 
 
+def _fold_bwd(dwf, w, s, mean, invstd, sums_g, need_w, need_gb):
+    """(dw, dgamma, dbeta) through the fold Wf = W*s, bf = beta - mean*s (ssg_bn_fold_bwd_f32); only what is asked for."""
+    o = w.shape[0]
+    dw = torch.empty_like(dwf) if need_w else None
+    dgb = torch.empty((2, o), dtype=torch.float32, device=w.device) if need_gb else None
+    wc = w.detach().contiguous()
+    call('ssg_bn_fold_bwd_f32', ptr(dwf), ptr(wc), o, wc.numel() // o, ptr(s), ptr(mean), ptr(invstd), ptr(sums_g), ptr(dw),
+         ptr(dgb[0]) if need_gb else None, ptr(dgb[1]) if need_gb else None, stream_ptr())
+    return dw, (dgb[0] if need_gb else None), (dgb[1] if need_gb else None)
+
+
+class _FrozenBasicBlockFn(torch.autograd.Function):
+    """BasicBlock whose two batch norms use their running statistics (eval mode / batchnorm.freeze_batch_norm), with autograd:
+    relu(conv3x3(x, Wf1) + bf1) -> relu(conv3x3(., Wf2) + bf2 + (conv1x1(x) | x)), Wf = W * gamma*invstd, bf = beta - mean*gamma*invstd.
+    The forward is the three launches of the eval branch of archs.BasicBlock (same kernels, same bits); no batch-norm pass runs in
+    either direction.  Saved: x1, x2, y1, out -- the two conv outputs of the train node (c1, c2) and its statistics never exist.
+    k1 / k2 = (s, mean, invstd) of bn1 / bn2."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, w1, g1, b1, w2, g2, b2, wsc, wf1, bf1, wf2, bf2, k1, k2, stride, record):
+        x1 = to_nhwc(x1)
+        x2 = to_nhwc(x2) if x2 is not None else None
+        y1 = _conv_fwd_impl(x1, x2, wf1, bf1, stride, 1, ACT_RELU, 0.0)
+        if wsc is not None:
+            r = _conv_fwd_impl(x1, x2, wsc, None, stride, 0, ACT_NONE, 0.0)
+        else:
+            if x2 is not None:
+                raise ValueError('identity shortcut with a two-tensor input')
+            r = x1
+        out = _conv_fwd_impl(y1, None, wf2, bf2, 1, 1, ACT_RELU, 0.0, res=r)
+        if record and any(ctx.needs_input_grad):          # `record`: the caller's grad mode (it is always off inside forward)
+            ctx.save_for_backward(x1, x2, y1, out, w1, w2, wsc, wf1, wf2, *k1, *k2)
+            ctx.stride = stride
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        x1, x2, y1, out, w1, w2, wsc, wf1, wf2, s1, m1, is1, s2, m2, is2 = ctx.saved_tensors
+        stride = ctx.stride
+        dout = to_nhwc(dout)
+        n, ca, h, w = x1.shape
+        cb = x2.shape[1] if x2 is not None else 0
+        need = ctx.needs_input_grad
+        need_x1, need_x2 = need[0], (x2 is not None and need[1])
+        need_w1, need_gb1, need_w2, need_gb2 = need[2], (need[3] or need[4]), need[5], (need[6] or need[7])
+        need_wsc = wsc is not None and need[8]
+        if stride != 1 and (need_x1 or need_x2):
+            raise NotImplementedError('strided BasicBlock input gradient')
+        # final ReLU: g2 = dout masked by out > 0 and its column sums (= d bf2) in one pass; g2 is also the shortcut branch's gradient
+        g2, _, sums2 = ops._frozen_bwd(None, out, dout, None, None, None, None, ACT_RELU, 0.0)
+        dw2 = dg2 = db2 = None
+        if need_w2 or need[6]:
+            dwf2 = _conv_wgrad_impl(y1, None, g2, w2.shape, 1, 1)
+            dw2, dg2, db2 = _fold_bwd(dwf2, w2, s2, m2, is2, sums2, need_w2, need_gb2)
+        elif need_gb2:
+            db2 = sums2[:w2.shape[0]].float()
+        dwsc = _conv_wgrad_impl(x1, x2, g2, wsc.shape, stride, 0) if need_wsc else None
+        dw1 = dg1 = db1 = dx1 = dx2 = None
+        if need_w1 or need_gb1 or need_x1 or need_x2:
+            dy1 = _conv_dgrad_impl(g2, wf2, 1, 1, y1.shape[2], y1.shape[3], 0, y1.shape[1])
+            g1, _, sums1 = ops._frozen_bwd(None, y1, dy1, None, None, None, None, ACT_RELU, 0.0)
+            del dy1
+            if need_w1 or need[3]:
+                dwf1 = _conv_wgrad_impl(x1, x2, g1, w1.shape, stride, 1)
+                dw1, dg1, db1 = _fold_bwd(dwf1, w1, s1, m1, is1, sums1, need_w1, need_gb1)
+            elif need_gb1:
+                db1 = sums1[:w1.shape[0]].float()
+            # the shortcut's gradient rides the residual epilogue of conv1's input gradient, as in _BasicBlockFn
+            if need_x1:
+                part = _conv_dgrad_impl(g2, wsc, 1, 0, h, w, 0, ca) if wsc is not None else g2
+                dx1 = _conv_dgrad_impl(g1, wf1, 1, 1, h, w, 0, ca, res=part)
+            if need_x2:
+                part = _conv_dgrad_impl(g2, wsc, 1, 0, h, w, ca, ca + cb)
+                dx2 = _conv_dgrad_impl(g1, wf1, 1, 1, h, w, ca, ca + cb, res=part)
+        return (dx1, dx2, dw1, dg1 if need[3] else None, db1 if need[4] else None, dw2, dg2 if need[6] else None,
+                db2 if need[7] else None, dwsc, None, None, None, None, None, None, None, None)
+
+
+def frozen_basic_block(x1, x2, conv1, bn1, conv2, bn2, shortcut_conv, folded, consts):
+    """BasicBlock over frozen batch norms as one autograd node.  `folded` = (wf1, bf1, wf2, bf2) and `consts` =
+    ((s1, mean1, invstd1), (s2, mean2, invstd2)) come from archs.BasicBlock's caches; nothing here writes a running statistic."""
+    wf1, bf1, wf2, bf2 = folded
+    return _FrozenBasicBlockFn.apply(x1, x2, conv1.weight, bn1.weight, bn1.bias, conv2.weight, bn2.weight, bn2.bias,
+                                     shortcut_conv.weight if shortcut_conv is not None else None, wf1, bf1, wf2, bf2,
+                                     consts[0], consts[1], int(conv1.stride[0]), torch.is_grad_enabled())
+
+
 def _spade_cat(wg, bg, wb, bb):
     """gamma and beta convs as ONE conv nhidden -> 2C: weights / biases concatenated along the output channels.  Cached on
     the gamma weight for one (storage, version, optimizer epoch) of the four tensors, so an eval loop concatenates once."""

@@ -34,12 +34,16 @@ __host__ RedGeom red_geom(long long P, int C, int Q = 1) {
 }
 
 // MODE 0: (sum x, sum x^2)      MODE 1: (sum g, sum g*xhat), g = dy * act'(y)      MODE 2: (sum x, -)
+// MODE 3: MODE 1 that also stores what a batch norm with CONSTANT statistics (eval mode, or a bias + activation) needs of the
+//         sweep: dx = g * scale (scale = NULL: g), dres = g.  x / mean may be NULL there (no xhat sum; x only where the
+//         activation gradient is recomputed from it).  Same accumulation expressions as MODE 1: the sums carry the same bits.
 template <int MODE, typename T>
 __global__ __launch_bounds__(RED_BLOCK) void col_reduce_kernel(
     const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy, long long P, int C,
     int ldx, int ldy, int lddy, const float* __restrict__ mean, const float* __restrict__ invstd,
     const float* __restrict__ scale, const float* __restrict__ shift, int act, float slope,
-    int TQ, int PR, long long rows_per_part, double* __restrict__ part /* [parts][2][Cpad] */) {
+    int TQ, int PR, long long rows_per_part, double* __restrict__ part /* [parts][2][Cpad] */,
+    T* __restrict__ dx, int lddx, T* __restrict__ dres, int lddres /* MODE 3 only */) {
   constexpr int Q = SsgQ<T>::value;              // channel quads per 16-byte access
   constexpr int V = 4 * Q;
   __shared__ double red[2][RED_BLOCK][V];
@@ -66,10 +70,26 @@ __global__ __launch_bounds__(RED_BLOCK) void col_reduce_kernel(
       if (c < C) { mu[e] = mean[c]; is[e] = invstd[c]; if ((!y || act == SSG_ACT_SWISH) && scale) { sc[e] = scale[c]; sh[e] = shift[c]; } }
     }
   }
+  if (MODE == 3 && cok) {
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const int c = V * cg + e;
+      if (c < C) {
+        if (mean) { mu[e] = mean[c]; is[e] = invstd[c]; }
+        if (scale) sc[e] = scale[c];
+        if (shift) sh[e] = shift[c];
+      }
+    }
+  }
   if (cok) {
     for (long long p = p0 + pr; p < p1; p += PR) {
       f32x4 xq[Q];
-      ldq(x + p * ldx + V * cg, xq);
+      if (MODE == 3 && !x) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) xq[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+      } else {
+        ldq(x + p * ldx + V * cg, xq);
+      }
       if (MODE == 0) {
 #pragma unroll
         for (int q = 0; q < Q; ++q)
@@ -102,7 +122,21 @@ __global__ __launch_bounds__(RED_BLOCK) void col_reduce_kernel(
               if (!(yv > 0.f)) g *= (act == SSG_ACT_RELU ? 0.f : slope);
             }
             const acc_t xh = ((acc_t)xv - (acc_t)mu[k]) * (acc_t)is[k];
-            s1[k] += (acc_t)g; s2[k] += (acc_t)g * xh;
+            s1[k] += (acc_t)g;
+            if (MODE == 1 || mean) s2[k] += (acc_t)g * xh;
+            if (MODE == 3) gq[q][e] = g;
+          }
+        }
+        if (MODE == 3) {
+          if (dres) stq(dres + p * lddres + V * cg, gq);
+          if (dx) {
+            if (scale) {
+#pragma unroll
+              for (int q = 0; q < Q; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) gq[q][e] *= sc[4 * q + e];
+            }
+            stq(dx + p * lddx + V * cg, gq);
           }
         }
       }
@@ -347,7 +381,7 @@ int run_reduce(const T* x, const T* y, const T* dy, long long P, int C, int ldx,
   const int C4 = 4 * Q * ((C + 4 * Q - 1) / (4 * Q));
   double* part = (double*)ws;
   hipLaunchKernelGGL((col_reduce_kernel<MODE, T>), dim3((unsigned)g.parts, (unsigned)g.groups), dim3(RED_BLOCK), 0, st, x, y, dy,
-                     P, C, ldx, ldy, lddy, mean, invstd, scale, shift, act, slope, g.TQ, g.PR, g.rows_per_part, part);
+                     P, C, ldx, ldy, lddy, mean, invstd, scale, shift, act, slope, g.TQ, g.PR, g.rows_per_part, part, (T*)nullptr, 0, (T*)nullptr, 0);
   SSG_LAUNCH_CHECK();
   hipLaunchKernelGGL(col_reduce_final_kernel, dim3((unsigned)((C + 31) / 32)), dim3(32 * FIN_LANES), 0, st, part, g.parts, C, C4, sums, fsum, count_out, fin, fin_count);
   SSG_LAUNCH_CHECK();
@@ -587,6 +621,81 @@ extern "C" int ssg_spade_modulate_bwd_sums_f32(const float* x, int ldx, const fl
   SSG_LAUNCH_CHECK();
   // sums[0:C] = sum dgamma, sums[C:2C] = sum dbeta (ssg_bn_workspace_bytes(P, C) bytes of workspace)
   hipLaunchKernelGGL(col_reduce_final_kernel, dim3((unsigned)((C + 31) / 32)), dim3(32 * FIN_LANES), 0, st, part, g.parts, C, C, sums, nullptr, 0.0, BnFin{}, 0.0);
+  SSG_LAUNCH_CHECK();
+  return SSG_OK;
+}
+
+// ------------------------------------------------------------------ frozen (running-statistics) batch norm, backward
+// Eval-mode batch norm is y = act(x*scale + shift (+ res)) with constants: its backward is one sweep (no second pass that
+// needs the sums first) -- col_reduce_kernel<3> stores dx / dres while it carries the two column sums.
+extern "C" int ssg_bn_frozen_bwd_f32(const float* x, const float* y, const float* dy, int64_t P, int C, int ldx, int ldy, int lddy,
+                                     const float* mean, const float* invstd, const float* scale, const float* shift, int act, float slope,
+                                     float* dx, int lddx, float* dres, int lddres, double* sums, void* ws, void* stream) {
+  SSG_REQUIRE(dy && sums && ws && P > 0 && C > 0, SSG_EINVAL, "bn_frozen_bwd: bad args");
+  SSG_REQUIRE(act == SSG_ACT_NONE || act == SSG_ACT_RELU || act == SSG_ACT_LRELU || act == SSG_ACT_SWISH, SSG_EINVAL, "bn_frozen_bwd: unknown activation");
+  SSG_REQUIRE((mean != nullptr) == (invstd != nullptr) && (!mean || x), SSG_EINVAL, "bn_frozen_bwd: mean / invstd come together and need x");
+  SSG_REQUIRE(act == SSG_ACT_NONE || (y && act != SSG_ACT_SWISH) || (x && scale && shift), SSG_EINVAL,
+              "bn_frozen_bwd: activation gradient needs y (ReLU family only) or (x, scale, shift)");
+  const bool use_y = y && (act == SSG_ACT_RELU || act == SSG_ACT_LRELU);
+  SSG_REQUIRE(C % 4 == 0 && lddy % 4 == 0 && lddy >= C && (!x || (ldx % 4 == 0 && ldx >= C)) && (!use_y || (ldy % 4 == 0 && ldy >= C)) &&
+                  (!dx || (lddx % 4 == 0 && lddx >= C)) && (!dres || (lddres % 4 == 0 && lddres >= C)) && ssg_aligned16(dy) && ssg_aligned16(x) &&
+                  (!use_y || ssg_aligned16(y)) && ssg_aligned16(dx) && ssg_aligned16(dres),
+              SSG_EALIGN, "bn_frozen_bwd: C / ld must be multiples of 4, ld >= C, rows 16-byte aligned");
+  const RedGeom g = red_geom(P, C, 1);
+  double* part = (double*)ws;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((col_reduce_kernel<3, float>), dim3((unsigned)g.parts, (unsigned)g.groups), dim3(RED_BLOCK), 0, st, x, use_y ? y : nullptr, dy,
+                     (long long)P, C, ldx, ldy, lddy, mean, invstd, scale, shift, act, slope, g.TQ, g.PR, g.rows_per_part, part, dx, lddx, dres, lddres);
+  SSG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(col_reduce_final_kernel, dim3((unsigned)((C + 31) / 32)), dim3(32 * FIN_LANES), 0, st, part, g.parts, C, C, sums, (float*)nullptr, 0.0,
+                     BnFin{}, 0.0);
+  SSG_LAUNCH_CHECK();
+  return SSG_OK;
+}
+
+namespace {
+// Gradients through the fold Wf[o] = W[o]*s[o], bf[o] = beta[o] - mean[o]*s[o], s = gamma*invstd: one workgroup per output channel,
+// every thread adds its strided products in fp64 (fp32 x fp32 is exact there), the 256 thread sums fold through LDS in a fixed tree.
+constexpr int FOLD_BLOCK = 256;
+__global__ __launch_bounds__(FOLD_BLOCK) void bn_fold_bwd_kernel(const float* __restrict__ dwf, const float* __restrict__ w, long long K,
+                                                                 const float* __restrict__ s, const float* __restrict__ mean,
+                                                                 const float* __restrict__ invstd, const double* __restrict__ sums_g,
+                                                                 float* __restrict__ dw, float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  __shared__ double red[FOLD_BLOCK];
+  const int o = blockIdx.x, tid = threadIdx.x;
+  const float* a = dwf + (size_t)o * K;
+  const float so = s[o];
+  double t = 0;
+  if (dgamma) {
+    const float* b = w + (size_t)o * K;
+    for (long long k = tid; k < K; k += FOLD_BLOCK) t += (double)a[k] * (double)b[k];
+  }
+  if (dw) {
+    float* d = dw + (size_t)o * K;
+    for (long long k = tid; k < K; k += FOLD_BLOCK) d[k] = a[k] * so;
+  }
+  if (!dgamma) return;                                   // uniform over the grid: no barrier is skipped by part of a block
+  red[tid] = t;
+  __syncthreads();
+  for (int h = FOLD_BLOCK / 2; h > 0; h >>= 1) {
+    if (tid < h) red[tid] += red[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const double sg = sums_g[o];
+    dgamma[o] = (float)((red[0] - (double)mean[o] * sg) * (double)invstd[o]);
+    dbeta[o] = (float)sg;
+  }
+}
+}  // namespace
+
+extern "C" int ssg_bn_fold_bwd_f32(const float* dwf, const float* w, int Cout, int64_t K, const float* s, const float* mean,
+                                   const float* invstd, const double* sums_g, float* dw, float* dgamma, float* dbeta, void* stream) {
+  SSG_REQUIRE(dwf && s && Cout > 0 && K > 0 && (dw || dgamma), SSG_EINVAL, "bn_fold_bwd: bad args");
+  SSG_REQUIRE((dgamma != nullptr) == (dbeta != nullptr), SSG_EINVAL, "bn_fold_bwd: dgamma and dbeta come together");
+  SSG_REQUIRE(!dgamma || (w && mean && invstd && sums_g), SSG_EINVAL, "bn_fold_bwd: dgamma / dbeta need w, mean, invstd, sums_g");
+  hipLaunchKernelGGL(bn_fold_bwd_kernel, dim3((unsigned)Cout), dim3(FOLD_BLOCK), 0, (hipStream_t)stream, dwf, w, (long long)K, s, mean, invstd, sums_g,
+                     dw, dgamma, dbeta);
   SSG_LAUNCH_CHECK();
   return SSG_OK;
 }
