@@ -211,11 +211,12 @@ typedef struct {
 int64_t ssg_conv2d_wgrad_workspace_bytes(const ssg_wgrad_desc* d);
 int ssg_conv2d_wgrad_in_affine_ok(const ssg_wgrad_desc* d);   /* ABI 8 */
 int ssg_conv2d_wgrad_f32(const ssg_wgrad_desc* d, void* stream);
-/* 0..2 = wgrad_kernel<128,128>/<128,64>/<128,32>, 30/31 = wgrad_halo_kernel<32,128>/<64,64> (3x3 stride-1
- * window kept in LDS; default for those), 20/21 = wgrad_dma_kernel<128,128>/<128,64> (default
- * for Cout > 32), 40/41 = wgrad_halo_x3_kernel<32,128>/<64,64> (the halo kernels with split operands, flags bit 0),
- * 15/16 = wgrad4_kernel (4x4x1 MFMA: dout <= 4 channels / in = 4 channels, the default for
- * those shapes), 13/14 = the opt-in VALU variants */
+/* 2 = wgrad_kernel<128,32> (Cout <= 32), 20/21 = wgrad_dma_kernel<128,128>/<128,64> (Cout > 64 / > 32), 30/31 =
+ * wgrad_halo_kernel<32,128>/<64,64> (3x3 stride-1 window kept in LDS, channel counts multiples of 32 / 64), 40/41 and 50/51 =
+ * the split-operand (x3) forms of 30/31 and 20/21 (flags bit 0), 60 = wgrad_k32_kernel (below), 15/16 = wgrad4_kernel (4x4x1
+ * MFMA: dout <= 4 channels / in = 4 channels), 17 = wgrad_tiny4_kernel (in = 4 channels, dout <= 8, 3x3; VALU), 18 =
+ * wgrad32_cin_kernel (in = 4 channels, 3x3, Cout >= 32 on >= 65536 pixels; 32x32x2 MFMA).  No other id is returned: Cout > 32
+ * always takes the DMA or halo kernels (no 0/1), and a thin plan is 10 + ssg_wgrad4_kind with kinds 5..8 (no 13/14). */
 int ssg_conv2d_wgrad_kernel_id(const ssg_wgrad_desc* d);
 /* 60 = wgrad_k32_kernel (conv_wgrad_k32.hip, round 4): the split-operand weight gradient of 3x3 stride-1 convs on
  * v_mfma_f32_16x16x32_bf16 (64-channel multiples on every side; flags bit 0).  ssg_wgrad_set_k32_mode(0 / 1) switches it off / on
