@@ -223,6 +223,22 @@ int ssg_conv2d_wgrad_kernel_id(const ssg_wgrad_desc* d);
  * at run time (default on, SSG_WGRAD_K32). */
 int ssg_wgrad_set_k32_mode(int mode);
 
+/* Opt-in bf16x1 weight gradient (conv_wgrad_k32_x1.hip; ops.train_precision('bf16x1')): the contract of ssg_conv2d_wgrad_f32 for the
+ * 3x3 stride-1 pad-1 conv, with both operands rounded once to bf16 (round to nearest even) and fp32 accumulation -- one MFMA per
+ * product instead of six.  An APPROXIMATION: |error| <= (2^-8 + 2^-18) * sum |in| |dout| plus the fp32 accumulation error;
+ * ssg_conv2d_wgrad_f32 never routes here.  A workgroup that meets a non-finite accumulator (an fp32 value >= 2^128 - 2^119 rounds
+ * to bf16 infinity) recomputes its tile from the fp32 operands, so the result class is that of the fp32 kernel.
+ * ssg_conv2d_wgrad_bf16x1_ok: 1 where the launch takes `d` -- the nine row-major taps (dy = t / 3 - 1, dx = t % 3 - 1, ky = t / 3,
+ *   kx = t % 3) at unit stride over the whole image (GH == H, GW == W), C1 % 64 == C2 % 64 == Cout % 64 == 0, Cin_real == C1 + C2,
+ *   GW >= 17, pixel strides multiples of 4, tensors within 32-bit byte offsets, in_scale == NULL -- else 0.  Pointers are not read.
+ * ssg_conv2d_wgrad_bf16x1_workspace_bytes: bytes of d->ws for the split-K slabs (0 where refused).
+ * ssg_conv2d_wgrad_bf16x1_f32 validates on the host and returns a status before any launch; d->flags is ignored.
+ * ssg_conv2d_wgrad_bf16x1_kernel_id: 72 = wgrad_k32_x1_kernel (profiling label), SSG_EINVAL where refused. */
+int ssg_conv2d_wgrad_bf16x1_ok(const ssg_wgrad_desc* d);
+int64_t ssg_conv2d_wgrad_bf16x1_workspace_bytes(const ssg_wgrad_desc* d);
+int ssg_conv2d_wgrad_bf16x1_f32(const ssg_wgrad_desc* d, void* stream);
+int ssg_conv2d_wgrad_bf16x1_kernel_id(const ssg_wgrad_desc* d);
+
 /* Attention gate of AttUNet (archs.py:115-144, `x * psi`): y[p][c] = x[p][c] * sigmoid(g[p]) with one gate
  * logit per pixel (g is the 1-channel BatchNorm output, pixel stride ldg); the sigmoid is folded in.
  * backward: dx = dy * s, dg[p] = (sum_c dy*x) * s * (1 - s) (written as a 4-float pixel: value, 0, 0, 0). */

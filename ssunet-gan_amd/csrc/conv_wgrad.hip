@@ -374,6 +374,22 @@ extern "C" int ssg_conv2d_wgrad_f32(const ssg_wgrad_desc* d, void* stream) {
   return SSG_OK;
 }
 
+// The ordered second stage alone, for a launcher outside this file (conv_wgrad_k32_x1.hip): `splits` slabs [9 * Cin][Cout] in d->ws
+// -> d->dw_oihw, wgrad_reduce_kernel as ssg_conv2d_wgrad_f32 launches it.
+int ssg_wgrad_reduce_launch(const ssg_wgrad_desc* d, int splits, hipStream_t st) {
+  RedArgs r;
+  r.ws = d->ws; r.dw = d->dw_oihw; r.splits = splits; r.M = d->ntaps * (d->C1 + d->C2); r.Cout = d->Cout; r.Cin = d->C1 + d->C2;
+  r.Cin_real = d->Cin_real; r.KH = d->KH; r.KW = d->KW; r.ntaps = d->ntaps;
+  for (int t = 0; t < SSG_MAX_TAPS; ++t) { r.ky[t] = t < d->ntaps ? d->ky[t] : 0; r.kx[t] = t < d->ntaps ? d->kx[t] : 0; }
+  const long long tot = (long long)r.M * d->Cout;
+  if (splits >= 256 && tot <= 32 * 1024)
+    hipLaunchKernelGGL(wgrad_reduce_kernel<32>, dim3((unsigned)ssg_cdiv(tot, 32)), dim3(1024), 0, st, r);
+  else
+    hipLaunchKernelGGL(wgrad_reduce_kernel<8>, dim3((unsigned)ssg_cdiv(tot, 32)), dim3(256), 0, st, r);
+  SSG_LAUNCH_CHECK();
+  return SSG_OK;
+}
+
 extern "C" int ssg_pack_weights_scaled_f32(const float* w_oihw, int O, int I, int KH, int KW, int transpose, int ntaps,
                                            const int* ky, const int* kx, int kmode, int Cred_pad, int Kp, const float* sigma, float* out,
                                            void* stream);

@@ -673,9 +673,10 @@ def conv2d_bf16x1_ok(x, weight, x2=None, res=None):
     return call('ssg_conv2d_bf16x1_ok', C.byref(_x1_desc(x, x2, weight, res))) != 0
 
 
-def _x1_pack(weight, wpk, kp, fmt):
+def _x1_pack(weight, wpk, kp, fmt, transpose=0, row0=0, rows=None):
     """The bf16 pack of `weight` (OIHW) for format `fmt`, built from its fp32 kmode-0 matrix `wpk`; cached on the weight tensor as
-    `_ssg_pack_bf16x1`, stamped like `_ssg_pack`."""
+    `_ssg_pack_bf16x1`, stamped like `_ssg_pack`.  transpose / row0 / rows: rows [row0, row0 + rows) of the TRANSPOSED matrix (an
+    input gradient for a channel slice of a concat input); such packs are keyed (transpose, row0, rows, fmt)."""
     stamp = (weight.data_ptr(), weight._version, _WEIGHT_EPOCH[0])
     cache = weight.__dict__.get('_ssg_pack_bf16x1')
     if cache is None or cache[0] != stamp:
@@ -684,12 +685,15 @@ def _x1_pack(weight, wpk, kp, fmt):
             weight._ssg_pack_bf16x1 = cache
         except Exception:
             pass
-    hit = cache[1].get(fmt)
+    if rows is None:
+        rows = weight.shape[0]
+    key = (transpose, row0, rows, fmt) if transpose else fmt
+    hit = cache[1].get(key)
     if hit is None:
-        nbytes = call('ssg_pack_weights_bf16x1_bytes', weight.shape[0], kp, fmt)
+        nbytes = call('ssg_pack_weights_bf16x1_bytes', rows, kp, fmt)
         hit = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
-        call('ssg_pack_weights_bf16x1', ptr(wpk), weight.shape[0], kp, fmt, ptr(hit), stream_ptr())
-        cache[1][fmt] = hit
+        call('ssg_pack_weights_bf16x1', wpk.data_ptr() + row0 * kp * 4, rows, kp, fmt, ptr(hit), stream_ptr())
+        cache[1][key] = hit
     return hit
 
 
@@ -736,6 +740,186 @@ def conv2d_bf16x1(x, weight, bias=None, act=ACT_NONE, slope=0.0, x2=None, res=No
         raise ValueError('conv2d_bf16x1: no bf16x1 kernel for x %s x2 %s weight %s res %s (conv2d_bf16x1_ok is False)' % (
             tuple(x.shape), None if x2 is None else tuple(x2.shape), tuple(weight.shape), None if res is None else tuple(res.shape)))
     return _conv_bf16x1_impl(x, weight, bias, act, slope, x2=x2, res=res)
+
+
+# ----------------------------------------------------------------------------- opt-in bf16x1 training
+# 'fp32 master weights, bf16 operands, fp32 accumulation' for the dense 3x3 stride-1 convs: forward and input gradient on
+# conv_halo_k32_x1_kernel (the input gradient is the same convolution on dy with the transposed pack and the taps (1 - ky, 1 - kx)),
+# weight gradient on wgrad_k32_x1_kernel (csrc/conv_wgrad_k32_x1.hip).  Every tensor in HBM stays fp32.  Chosen by the caller:
+# ops.conv2d and its autograd node never come here.
+_WGRAD_X1_LABELS = {72: 'wgrad_k32_x1_kernel'}
+_X1_TAPS_T = [(ky, kx, 1 - ky, 1 - kx) for ky in range(3) for kx in range(3)]
+_TRAIN_PRECISIONS = ('fp32', 'bf16x1')
+_TRAIN_PRECISION = ['fp32']
+
+
+class train_precision(object):
+    """with ops.train_precision('bf16x1'): ...   -- autograd nodes that have a bf16x1 route (blocks._BasicBlockFn,
+    blocks._FrozenBasicBlockFn) run their 3x3 stride-1 convs, forward, input gradient and weight gradient, with both operands
+    rounded once to bf16 (fp32 accumulation, fp32 tensors: an approximation) wherever the kernels' predicates hold, and stay on the
+    fp32-class kernels elsewhere.  'fp32' (the default) launches exactly what runs without the context.  A node reads the mode in
+    its forward and keeps it: its backward uses the forward's mode whatever is set when .backward() runs."""
+
+    def __init__(self, mode):
+        if mode not in _TRAIN_PRECISIONS:
+            raise ValueError('train_precision: unknown mode %r (one of %s)' % (mode, ', '.join(_TRAIN_PRECISIONS)))
+        self.mode = mode
+
+    def __enter__(self):
+        self.prev = _TRAIN_PRECISION[0]; _TRAIN_PRECISION[0] = self.mode
+        return self
+
+    def __exit__(self, *a):
+        _TRAIN_PRECISION[0] = self.prev
+
+
+def train_precision_mode():
+    """The mode the innermost `train_precision` block set ('fp32' outside any)."""
+    return _TRAIN_PRECISION[0]
+
+
+def _wgrad_x1_desc(x1, x2, dy, weight_shape):
+    o, i, kh, kw = weight_shape
+    n, c1, h, w = x1.shape
+    d = WgradDesc()
+    d.in1 = x1.data_ptr(); d.C1 = c1; d.ld1 = _ld(x1)
+    if x2 is not None:
+        d.in2 = x2.data_ptr(); d.C2 = x2.shape[1]; d.ld2 = _ld(x2)
+    else:
+        d.in2 = None; d.C2 = 0; d.ld2 = 0
+    d.N, d.H, d.W = n, h, w
+    d.dout = dy.data_ptr(); d.Cout = o; d.ldd = _ld(dy); d.GH, d.GW = dy.shape[2], dy.shape[3]
+    d.in_sy = d.in_sx = 1
+    _fill_taps(d, _X1_TAPS)
+    for t, (ky, kx, _, _) in enumerate(_X1_TAPS):
+        d.ky[t] = ky; d.kx[t] = kx
+    d.KH, d.KW, d.Cin_real = kh, kw, i
+    d.dw_oihw = None
+    d.ws = None; d.ws_bytes = 0
+    d.flags = 0
+    d.in_scale = None; d.in_shift = None; d.in_act = ACT_NONE; d.in_slope = 0.0
+    return d
+
+
+def _conv_wgrad_bf16x1_impl(x1, x2, dy, weight_shape):
+    """Weight gradient [O, I, 3, 3] of the 3x3 stride-1 pad-1 conv of cat(x1, x2) with x and dy rounded once to bf16
+    (ssg_conv2d_wgrad_bf16x1_f32).  Returns None, with nothing launched, where ssg_conv2d_wgrad_bf16x1_ok refuses: the caller
+    then takes _conv_wgrad_impl for this launch."""
+    o, i, kh, kw = weight_shape
+    if (kh, kw) != (3, 3) or tuple(dy.shape[2:]) != tuple(x1.shape[2:]) or x1.shape[1] + (x2.shape[1] if x2 is not None else 0) != i:
+        return None
+    d = _wgrad_x1_desc(x1, x2, dy, weight_shape)
+    if not call('ssg_conv2d_wgrad_bf16x1_ok', C.byref(d)):
+        return None
+    n, _, h, w = x1.shape
+    dw = torch.empty((o, i, 3, 3), device=dy.device, dtype=torch.float32)
+    d.dw_oihw = dw.data_ptr()
+    ws = _ws(call('ssg_conv2d_wgrad_bf16x1_workspace_bytes', C.byref(d)), dy.device)
+    d.ws = ws.data_ptr(); d.ws_bytes = ws.numel() * 8
+    label = None
+    if PROFILE is not None:
+        label = _WGRAD_X1_LABELS.get(call('ssg_conv2d_wgrad_bf16x1_kernel_id', C.byref(d)), '?')
+        if PROFILE_SHAPES:
+            label += ' n%d %dx%d cin%d cout%d k3 s1' % (n, h, w, i, o)
+    with _Timed(label, 2.0 * n * h * w * o * i * 9):
+        call('ssg_conv2d_wgrad_bf16x1_f32', C.byref(d), stream_ptr())
+    return dw
+
+
+def _conv_dgrad_bf16x1_impl(dy, weight, h, w, c_lo, c_hi, res=None):
+    """Input gradient of the 3x3 stride-1 pad-1 conv for input channels [c_lo, c_hi) with dy and the weight rounded once to bf16:
+    conv_halo_k32_x1_kernel on dy with rows [c_lo, c_hi) of the transposed kmode-0 pack and the taps (1 - ky, 1 - kx); `res` is
+    added in the epilogue.  Returns None, with nothing launched, where ssg_conv2d_bf16x1_ok refuses (the caller then takes
+    _conv_dgrad_impl for this launch)."""
+    o, i, kh, kw = weight.shape
+    n, _, oh, ow = dy.shape
+    rows = c_hi - c_lo
+    if (kh, kw) != (3, 3) or (oh, ow) != (h, w) or o % 16 or rows <= 0:
+        return None
+    d = _x1_desc(dy, None, weight, res)
+    d.Cout = rows; d.ldo = pad4(rows); d.Kp = 9 * o
+    _fill_taps(d, _X1_TAPS_T)
+    if not call('ssg_conv2d_bf16x1_ok', C.byref(d)):
+        return None
+    wpk, kp, kmode = _pack(weight, 1, _X1_TAPS_T, o, o)
+    dx = new_nhwc(n, rows, h, w, dy.device)
+    d.w = wpk.data_ptr() + c_lo * kp * 4; d.Kp = kp; d.kmode = kmode
+    d.out = dx.data_ptr(); d.ldo = _ld(dx)
+    fmt = call('ssg_conv2d_bf16x1_ok', C.byref(d))
+    if not fmt:
+        return None
+    pack = _x1_pack(weight, wpk, kp, fmt, transpose=1, row0=c_lo, rows=rows)
+    label = None
+    if PROFILE is not None:
+        label = _X1_LABELS.get(call('ssg_conv2d_bf16x1_kernel_id', C.byref(d)), '?')
+        if PROFILE_SHAPES:
+            label += ' n%d %dx%d cin%d cout%d taps9 s1/1' % (n, h, w, o, rows)
+    with _Timed(label, 2.0 * n * h * w * o * rows * 9):
+        call('ssg_conv2d_bf16x1_f32', C.byref(d), ptr(pack), stream_ptr())
+    return dx
+
+
+def _conv_bwd_bf16x1(x1, x2, weight, dy, need_x1, need_x2, need_w):
+    """The three gradients of a routed 3x3 conv under train_precision('bf16x1'): each on the bf16x1 kernel where its predicate
+    holds, on the fp32-class kernel for that one launch where it refuses."""
+    n, c1, h, w = x1.shape
+    dx1 = dx2 = dw = None
+    if need_x1:
+        dx1 = _conv_dgrad_bf16x1_impl(dy, weight, h, w, 0, c1)
+        if dx1 is None:
+            dx1 = _conv_dgrad_impl(dy, weight, 1, 1, h, w, 0, c1)
+    if x2 is not None and need_x2:
+        dx2 = _conv_dgrad_bf16x1_impl(dy, weight, h, w, c1, c1 + x2.shape[1])
+        if dx2 is None:
+            dx2 = _conv_dgrad_impl(dy, weight, 1, 1, h, w, c1, c1 + x2.shape[1])
+    if need_w:
+        dw = _conv_wgrad_bf16x1_impl(x1, x2, dy, weight.shape)
+        if dw is None:
+            dw = _conv_wgrad_impl(x1, x2, dy, weight.shape, 1, 1)
+    return dx1, dx2, dw
+
+
+class _Conv2dBf16x1(torch.autograd.Function):
+    """conv2d_bf16x1_train: act(conv3x3(cat(x, x2)) + bias + res), all three directions on the one-term bf16 kernels."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, weight, bias, act, slope, res):
+        x1 = to_nhwc(x1)
+        x2 = to_nhwc(x2) if x2 is not None else None
+        res = to_nhwc(res) if res is not None else None
+        y = _conv_bf16x1_impl(x1, weight, bias, act, slope, x2=x2, res=res)
+        ctx.cfg = (act, slope)
+        ctx.save_for_backward(x1, x2, weight, y if act != ACT_NONE else None)
+        ctx.has_bias = bias is not None
+        ctx.has_res = res is not None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x1, x2, weight, y = ctx.saved_tensors
+        act, slope = ctx.cfg
+        dy = to_nhwc(dy)
+        if act != ACT_NONE:
+            dy = _act_bwd(y, dy, act, slope)
+        dx1, dx2, dw = _conv_bwd_bf16x1(x1, x2, weight, dy, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        db = _channel_sum(dy, weight.shape[0]) if (ctx.has_bias and ctx.needs_input_grad[3]) else None
+        dres = dy if (ctx.has_res and ctx.needs_input_grad[6]) else None      # residual joins before the activation
+        return dx1, dx2, dw, db, None, None, dres
+
+
+def conv2d_bf16x1_train(x, weight, bias=None, act=ACT_NONE, slope=0.0, x2=None, res=None):
+    """The differentiable form of `conv2d_bf16x1`: forward on conv_halo_k32_x1_kernel, gradients for x, x2 and res on the same
+    kernel (dy and the transposed weight rounded to bf16), weight gradient on wgrad_k32_x1_kernel (x and dy rounded), bias gradient
+    by the fp32 channel sum.  A gradient whose own predicate refuses (a 32-channel slice, say) runs on the fp32-class kernel.
+    Raises ValueError where `conv2d_bf16x1_ok` is false; there is no CPU fallback."""
+    for t in (x, weight, bias, x2, res):
+        if t is not None:
+            _lib.require_gpu(t)
+    if not conv2d_bf16x1_ok(x, weight, x2=x2, res=res):
+        raise ValueError('conv2d_bf16x1_train: no bf16x1 kernel for x %s x2 %s weight %s res %s (conv2d_bf16x1_ok is False)' % (
+            tuple(x.shape), None if x2 is None else tuple(x2.shape), tuple(weight.shape), None if res is None else tuple(res.shape)))
+    return _Conv2dBf16x1.apply(x, x2, weight, bias, int(act), float(slope), res)
 
 
 # ----------------------------------------------------------------------------- linear (as 1x1 conv over a 1 x N "image")

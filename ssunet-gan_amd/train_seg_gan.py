@@ -88,9 +88,12 @@ class _params_frozen(object):
 
 
 def gan_step(input, target, generator, discriminator, criterion, adversarial_loss_criterion, content_loss_criterion,
-             optimizer_g, optimizer_d, num_class, sync_g=None, sync_d=None):
-    """One iteration of train_seg_gan.py:182-233.  Returns device scalars (loss, iou, dice, closs, adv_g, adv_d)."""
-    with _stage('ssg.G_forward'):
+             optimizer_g, optimizer_d, num_class, sync_g=None, sync_d=None, precision='fp32'):
+    """One iteration of train_seg_gan.py:182-233.  Returns device scalars (loss, iou, dice, closs, adv_g, adv_d).
+    precision: 'fp32' (default) or 'bf16x1' -- ops.train_precision around the GENERATOR's forward and the backward that reaches
+    it (its BasicBlocks then run their 3x3 convs with bf16 operands and fp32 accumulation); the discriminator, the losses, the
+    parameters, the gradients and the optimizer state stay fp32 in either mode."""
+    with _stage('ssg.G_forward'), ops.train_precision(precision):
         generator_output = generator(input)                                    # :188
         generator_output = ops.nan_to_zero_(generator_output)                  # :190
     fused = isinstance(criterion, BCEDiceLoss) and isinstance(content_loss_criterion, nn.MSELoss) \
@@ -122,7 +125,8 @@ def gan_step(input, target, generator, discriminator, criterion, adversarial_los
     with _stage('ssg.G_step_backward'):
         if sync_g is not None:
             sync_g.begin()
-        perceptual_loss.backward()
+        with ops.train_precision(precision):
+            perceptual_loss.backward()
         if sync_g is not None:
             sync_g.finish()
     with _stage('ssg.G_optimizer'):
@@ -161,7 +165,7 @@ def train(epoch, config, train_loader, generator, discriminator, criterion, adve
         target = target.cuda(non_blocking=True)
         loss, iou, dice, _, _, _ = gan_step(input, target, generator, discriminator, criterion,
                                              adversarial_loss_criterion, content_loss_criterion, optimizer_g, optimizer_d,
-                                             num_class, sync_g, sync_d)
+                                             num_class, sync_g, sync_d, precision=config.get('precision', 'fp32'))
         n = input.size(0)
         avg_meters['loss'].update(loss, n)
         avg_meters['iou'].update(iou, n)
