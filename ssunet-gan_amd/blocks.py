@@ -12,38 +12,16 @@ import ctypes as C
 import torch
 
 from . import ops
-from ._lib import ACT_NONE, ACT_RELU, ConvDesc, call, ptr, stream_ptr
+from ._lib import ACT_NONE, ACT_RELU, call, ptr, stream_ptr
 from .ops import (_act_bwd, _bn_bwd_impl, _bn_fwd_impl, _channel_sum, _conv_dgrad_impl, _conv_fwd_impl, _conv_wgrad_impl,
                   _ld, new_nhwc, to_nhwc)
 
 
 # ----------------------------------------------------------------------------- ops.train_precision('bf16x1')
-# The two 3x3 stride-1 convs of a BasicBlock on the one-term bf16 kernels, each launch only where its own predicate holds
+# `x1m` is the mode a node's FORWARD read (and its stride is 1): the node then passes precision='bf16x1' to its two 3x3 convs in
+# all three directions.  Each launch runs on the one-term bf16 kernel only where its own predicate holds
 # (ssg_conv2d_bf16x1_ok / ssg_conv2d_wgrad_bf16x1_ok: 64-channel multiples, >= 17 pixels wide); a refused launch runs on the
-# fp32-class kernel it runs on today.  The 1x1 shortcut never comes here.  `x1m` is the mode the node's FORWARD read.
-def _fwd3_x1(a, b, w, bias, act, res=None):
-    """The routed forward conv, or None (nothing launched) where the bf16x1 kernel does not take it."""
-    if not ops.conv2d_bf16x1_ok(a, w, x2=b, res=res):
-        return None
-    return ops._conv_bf16x1_impl(a, w, bias, act, 0.0, x2=b, res=res)
-
-
-def _wgrad3(x1m, a, b, dy, shape, stride):
-    if x1m and stride == 1:
-        dw = ops._conv_wgrad_bf16x1_impl(a, b, dy, shape)
-        if dw is not None:
-            return dw
-    return _conv_wgrad_impl(a, b, dy, shape, stride, 1)
-
-
-def _dgrad3(x1m, dy, w, h, wd, c_lo, c_hi, res=None):
-    if x1m:
-        dx = ops._conv_dgrad_bf16x1_impl(dy, w, h, wd, c_lo, c_hi, res=res)
-        if dx is not None:
-            return dx
-    return _conv_dgrad_impl(dy, w, 1, 1, h, wd, c_lo, c_hi, res=res)
-
-
+# fp32-class kernel it runs on today.  The 1x1 shortcut always passes 'fp32'.
 class _BasicBlockFn(torch.autograd.Function):
     """relu(bn1(conv3x3(x))) -> bn2(conv3x3(.)) -> (+ conv1x1(x) | + x) -> relu, x = cat(x1, x2)."""
 
@@ -52,15 +30,16 @@ class _BasicBlockFn(torch.autograd.Function):
         x1 = to_nhwc(x1)
         x2 = to_nhwc(x2) if x2 is not None else None
         ctx.x1m = x1m = ops.train_precision_mode() == 'bf16x1' and stride == 1
-        if x1m:
-            return _BasicBlockFn._forward_x1(ctx, x1, x2, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, wsc, eps1, mom1, eps2, mom2, var_mode, group)
-        # batch-norm statistics ride the producing conv's epilogue where its kernel has one (part = None otherwise)
-        c1, part1 = _conv_fwd_impl(x1, x2, w1, None, stride, 1, ACT_NONE, 0.0, want_bn=True)
+        p3 = 'bf16x1' if x1m else 'fp32'
+        # batch-norm statistics ride the producing conv's epilogue where its kernel has one (part = None otherwise: the bf16x1
+        # launcher has none, so behind a routed conv the batch norm runs its own statistics pass)
+        c1, part1 = _conv_fwd_impl(x1, x2, w1, None, stride, 1, ACT_NONE, 0.0, want_bn=True, precision=p3)
         # relu(bn1(c1)) is applied on conv2's INPUT where its kernel can (the split-operand k32 tiles): y1 is never written, the
-        # backward's weight gradient reads c1 through the same transform and the ReLU mask is recomputed from c1 as before
+        # backward's weight gradient reads c1 through the same transform and the ReLU mask is recomputed from c1 as before.
+        # Off under bf16x1, also for a block whose first conv was refused and so has a part1.
         y1 = None
         c2 = None
-        if ops.BN_FUSE_INPUT and part1 is not None:
+        if ops.BN_FUSE_INPUT and part1 is not None and not x1m:
             _, st1, cnt1 = _bn_fwd_impl(c1, g1, b1, rm1, rv1, None, eps1, mom1, ACT_RELU, 0.0, var_mode, group, part=part1, apply=False)
             r = _conv_fwd_impl(c1, None, w2, None, 1, 1, ACT_NONE, 0.0, want_bn=True, in_affine=(st1[2], st1[3], ACT_RELU, 0.0))
             if r is not None:
@@ -71,7 +50,7 @@ class _BasicBlockFn(torch.autograd.Function):
         else:
             y1, st1, cnt1 = _bn_fwd_impl(c1, g1, b1, rm1, rv1, None, eps1, mom1, ACT_RELU, 0.0, var_mode, group, part=part1)
         if c2 is None:
-            c2, part2 = _conv_fwd_impl(y1, None, w2, None, 1, 1, ACT_NONE, 0.0, want_bn=True)
+            c2, part2 = _conv_fwd_impl(y1, None, w2, None, 1, 1, ACT_NONE, 0.0, want_bn=True, precision=p3)
         if wsc is not None:
             sc = _conv_fwd_impl(x1, x2, wsc, None, stride, 0, ACT_NONE, 0.0)
         else:
@@ -84,59 +63,12 @@ class _BasicBlockFn(torch.autograd.Function):
         return out
 
     @staticmethod
-    def _forward_x1(ctx, x1, x2, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, wsc, eps1, mom1, eps2, mom2, var_mode, group):
-        """train_precision('bf16x1'): the bf16x1 launcher has no statistics epilogue (no bnpart), so each batch norm runs its own
-        statistics pass (part = None) behind a routed conv; ops.BN_FUSE_INPUT is ignored."""
-        c1, part1 = _fwd3_x1(x1, x2, w1, None, ACT_NONE), None
-        if c1 is None:
-            c1, part1 = _conv_fwd_impl(x1, x2, w1, None, 1, 1, ACT_NONE, 0.0, want_bn=True)
-        y1, st1, cnt1 = _bn_fwd_impl(c1, g1, b1, rm1, rv1, None, eps1, mom1, ACT_RELU, 0.0, var_mode, group, part=part1)
-        c2, part2 = _fwd3_x1(y1, None, w2, None, ACT_NONE), None
-        if c2 is None:
-            c2, part2 = _conv_fwd_impl(y1, None, w2, None, 1, 1, ACT_NONE, 0.0, want_bn=True)
-        if wsc is not None:
-            sc = _conv_fwd_impl(x1, x2, wsc, None, 1, 0, ACT_NONE, 0.0)
-        else:
-            if x2 is not None:
-                raise ValueError('identity shortcut with a two-tensor input')
-            sc = x1
-        out, st2, cnt2 = _bn_fwd_impl(c2, g2, b2, rm2, rv2, sc, eps2, mom2, ACT_RELU, 0.0, var_mode, group, part=part2)
-        ctx.save_for_backward(x1, x2, c1, y1, c2, out, w1, g1, w2, g2, wsc, st1, st2)
-        ctx.cfg = (1, group, cnt1, cnt2)
-        return out
-
-    @staticmethod
-    def _backward_x1(ctx, dout):
-        """The backward of _forward_x1: same schedule as the fp32 one without the fused routes (ops.BN_BWD_EPILOGUE is ignored)."""
-        x1, x2, c1, y1, c2, out, w1, g1, w2, g2, wsc, st1, st2 = ctx.saved_tensors
-        _, group, cnt1, cnt2 = ctx.cfg
-        dout = to_nhwc(dout)
-        n, ca, h, w = x1.shape
-        cb = x2.shape[1] if x2 is not None else 0
-        need_x1, need_x2 = ctx.needs_input_grad[0], (x2 is not None and ctx.needs_input_grad[1])
-        dc2, g, dg2, db2 = _bn_bwd_impl(c2, out, dout, g2, st2, ACT_RELU, 0.0, group, cnt2, want_dres=True)
-        dw2 = _wgrad3(True, y1, None, dc2, w2.shape, 1)
-        dy1 = _dgrad3(True, dc2, w2, h, w, 0, c1.shape[1])
-        dc1, _, dg1, db1 = _bn_bwd_impl(c1, y1, dy1, g1, st1, ACT_RELU, 0.0, group, cnt1, want_dres=False, had_res=False)
-        dw1 = _wgrad3(True, x1, x2, dc1, w1.shape, 1)
-        dwsc = _conv_wgrad_impl(x1, x2, g, wsc.shape, 1, 0) if wsc is not None else None
-        dx1 = dx2 = None
-        if need_x1:
-            part = _conv_dgrad_impl(g, wsc, 1, 0, h, w, 0, ca) if wsc is not None else g
-            dx1 = _dgrad3(True, dc1, w1, h, w, 0, ca, res=part)
-        if need_x2:
-            part = _conv_dgrad_impl(g, wsc, 1, 0, h, w, ca, ca + cb)
-            dx2 = _dgrad3(True, dc1, w1, h, w, ca, ca + cb, res=part)
-        return (dx1, dx2, dw1, dg1, db1, None, None, dw2, dg2, db2, None, None, dwsc,
-                None, None, None, None, None, None, None)
-
-    @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dout):
-        if ctx.x1m:
-            return _BasicBlockFn._backward_x1(ctx, dout)
         x1, x2, c1, y1, c2, out, w1, g1, w2, g2, wsc, st1, st2 = ctx.saved_tensors
         stride, group, cnt1, cnt2 = ctx.cfg
+        x1m = ctx.x1m                                    # the forward's train_precision mode, whatever is set now
+        p3 = 'bf16x1' if x1m else 'fp32'
         dout = to_nhwc(dout)
         n, ca, h, w = x1.shape
         cb = x2.shape[1] if x2 is not None else 0
@@ -151,27 +83,28 @@ class _BasicBlockFn(torch.autograd.Function):
                 dw2 = _conv_wgrad_impl(y1w, None, dc2, w2.shape, 1, 1)
                 del y1w
         else:
-            dw2 = _conv_wgrad_impl(y1, None, dc2, w2.shape, 1, 1)
+            dw2 = _conv_wgrad_impl(y1, None, dc2, w2.shape, 1, 1, precision=p3)
         # bn1's backward sums ride the epilogue of the input gradient that produces d(relu(bn1(c1))) where its kernel has one
-        # (ssg_conv_desc.bwd_x: the k32 tiles): the reduce pass over (dy1, c1) goes, the apply pass reads the already masked gradient
+        # (ssg_conv_desc.bwd_x: the k32 tiles): the reduce pass over (dy1, c1) goes, the apply pass reads the already masked gradient.
+        # Off under bf16x1.
         r = _conv_dgrad_impl(dc2, w2, 1, 1, c1.shape[2], c1.shape[3], 0, c1.shape[1], bwd_stats=(c1, st1, ACT_RELU, 0.0)) \
-            if ops.BN_BWD_EPILOGUE else None
+            if ops.BN_BWD_EPILOGUE and not x1m else None
         if r is not None:
             dc1, dg1, db1 = ops._bn_bwd_from_partials(c1, r[0], r[1], g1, st1, group, cnt1)
         else:
-            dy1 = _conv_dgrad_impl(dc2, w2, 1, 1, c1.shape[2], c1.shape[3], 0, c1.shape[1])
+            dy1 = _conv_dgrad_impl(dc2, w2, 1, 1, c1.shape[2], c1.shape[3], 0, c1.shape[1], precision=p3)
             dc1, _, dg1, db1 = _bn_bwd_impl(c1, y1, dy1, g1, st1, ACT_RELU, 0.0, group, cnt1, want_dres=False, had_res=False)
-        dw1 = _conv_wgrad_impl(x1, x2, dc1, w1.shape, stride, 1)
+        dw1 = _conv_wgrad_impl(x1, x2, dc1, w1.shape, stride, 1, precision=p3)
         dwsc = _conv_wgrad_impl(x1, x2, g, wsc.shape, stride, 0) if wsc is not None else None
         dx1 = dx2 = None
         if stride != 1 and (need_x1 or need_x2):
             raise NotImplementedError('strided BasicBlock input gradient')
         if need_x1:
             part = _conv_dgrad_impl(g, wsc, 1, 0, h, w, 0, ca) if wsc is not None else g
-            dx1 = _conv_dgrad_impl(dc1, w1, 1, 1, h, w, 0, ca, res=part)
+            dx1 = _conv_dgrad_impl(dc1, w1, 1, 1, h, w, 0, ca, res=part, precision=p3)
         if need_x2:
             part = _conv_dgrad_impl(g, wsc, 1, 0, h, w, ca, ca + cb)
-            dx2 = _conv_dgrad_impl(dc1, w1, 1, 1, h, w, ca, ca + cb, res=part)
+            dx2 = _conv_dgrad_impl(dc1, w1, 1, 1, h, w, ca, ca + cb, res=part, precision=p3)
         return (dx1, dx2, dw1, dg1, db1, None, None, dw2, dg2, db2, None, None, dwsc,
                 None, None, None, None, None, None, None)
 
@@ -215,18 +148,15 @@ class _FrozenBasicBlockFn(torch.autograd.Function):
         # train_precision('bf16x1'): the folded convs with their bias / ReLU / residual epilogues on the bf16x1 kernel, as the eval
         # path under infer_precision; only a forward that records a graph reads the mode
         x1m = record and any(ctx.needs_input_grad) and ops.train_precision_mode() == 'bf16x1' and stride == 1
-        y1 = _fwd3_x1(x1, x2, wf1, bf1, ACT_RELU) if x1m else None
-        if y1 is None:
-            y1 = _conv_fwd_impl(x1, x2, wf1, bf1, stride, 1, ACT_RELU, 0.0)
+        p3 = 'bf16x1' if x1m else 'fp32'
+        y1 = _conv_fwd_impl(x1, x2, wf1, bf1, stride, 1, ACT_RELU, 0.0, precision=p3)
         if wsc is not None:
             r = _conv_fwd_impl(x1, x2, wsc, None, stride, 0, ACT_NONE, 0.0)
         else:
             if x2 is not None:
                 raise ValueError('identity shortcut with a two-tensor input')
             r = x1
-        out = _fwd3_x1(y1, None, wf2, bf2, ACT_RELU, res=r) if x1m else None
-        if out is None:
-            out = _conv_fwd_impl(y1, None, wf2, bf2, 1, 1, ACT_RELU, 0.0, res=r)
+        out = _conv_fwd_impl(y1, None, wf2, bf2, 1, 1, ACT_RELU, 0.0, res=r, precision=p3)
         if record and any(ctx.needs_input_grad):          # `record`: the caller's grad mode (it is always off inside forward)
             ctx.save_for_backward(x1, x2, y1, out, w1, w2, wsc, wf1, wf2, *k1, *k2)
             ctx.stride = stride
@@ -238,7 +168,7 @@ class _FrozenBasicBlockFn(torch.autograd.Function):
     def backward(ctx, dout):
         x1, x2, y1, out, w1, w2, wsc, wf1, wf2, s1, m1, is1, s2, m2, is2 = ctx.saved_tensors
         stride = ctx.stride
-        x1m = ctx.x1m                                    # the forward's train_precision mode, whatever is set now
+        p3 = 'bf16x1' if ctx.x1m else 'fp32'             # the forward's train_precision mode, whatever is set now
         dout = to_nhwc(dout)
         n, ca, h, w = x1.shape
         cb = x2.shape[1] if x2 is not None else 0
@@ -252,28 +182,28 @@ class _FrozenBasicBlockFn(torch.autograd.Function):
         g2, _, sums2 = ops._frozen_bwd(None, out, dout, None, None, None, None, ACT_RELU, 0.0)
         dw2 = dg2 = db2 = None
         if need_w2 or need[6]:
-            dwf2 = _wgrad3(x1m, y1, None, g2, w2.shape, 1)
+            dwf2 = _conv_wgrad_impl(y1, None, g2, w2.shape, 1, 1, precision=p3)
             dw2, dg2, db2 = _fold_bwd(dwf2, w2, s2, m2, is2, sums2, need_w2, need_gb2)
         elif need_gb2:
             db2 = sums2[:w2.shape[0]].float()
         dwsc = _conv_wgrad_impl(x1, x2, g2, wsc.shape, stride, 0) if need_wsc else None
         dw1 = dg1 = db1 = dx1 = dx2 = None
         if need_w1 or need_gb1 or need_x1 or need_x2:
-            dy1 = _dgrad3(x1m, g2, wf2, y1.shape[2], y1.shape[3], 0, y1.shape[1])
+            dy1 = _conv_dgrad_impl(g2, wf2, 1, 1, y1.shape[2], y1.shape[3], 0, y1.shape[1], precision=p3)
             g1, _, sums1 = ops._frozen_bwd(None, y1, dy1, None, None, None, None, ACT_RELU, 0.0)
             del dy1
             if need_w1 or need[3]:
-                dwf1 = _wgrad3(x1m, x1, x2, g1, w1.shape, stride)
+                dwf1 = _conv_wgrad_impl(x1, x2, g1, w1.shape, stride, 1, precision=p3)
                 dw1, dg1, db1 = _fold_bwd(dwf1, w1, s1, m1, is1, sums1, need_w1, need_gb1)
             elif need_gb1:
                 db1 = sums1[:w1.shape[0]].float()
             # the shortcut's gradient rides the residual epilogue of conv1's input gradient, as in _BasicBlockFn
             if need_x1:
                 part = _conv_dgrad_impl(g2, wsc, 1, 0, h, w, 0, ca) if wsc is not None else g2
-                dx1 = _dgrad3(x1m, g1, wf1, h, w, 0, ca, res=part)
+                dx1 = _conv_dgrad_impl(g1, wf1, 1, 1, h, w, 0, ca, res=part, precision=p3)
             if need_x2:
                 part = _conv_dgrad_impl(g2, wsc, 1, 0, h, w, ca, ca + cb)
-                dx2 = _dgrad3(x1m, g1, wf1, h, w, ca, ca + cb, res=part)
+                dx2 = _conv_dgrad_impl(g1, wf1, 1, 1, h, w, ca, ca + cb, res=part, precision=p3)
         return (dx1, dx2, dw1, dg1 if need[3] else None, db1 if need[4] else None, dw2, dg2 if need[6] else None,
                 db2 if need[7] else None, dwsc, None, None, None, None, None, None, None, None)
 
@@ -297,10 +227,7 @@ def _spade_cat(wg, bg, wb, bb):
     with torch.no_grad():
         w = torch.cat([wg.detach(), wb.detach()], 0).contiguous()
         b = torch.cat([bg.detach(), bb.detach()], 0).contiguous()
-    try:
-        wg._ssg_gb_cat = (stamp, w, b)
-    except Exception:
-        pass
+    ops._attach(wg, '_ssg_gb_cat', (stamp, w, b))
     return w, b
 
 
@@ -314,17 +241,8 @@ def _spade_fused_fwd(x, a, wgb, bgb, pad, out):
         return None
     taps = ops._taps_fwd(kh, kw, pad)
     wpk, kp, kmode = ops._pack(wgb, 0, taps, cin, cin)
-    d = ConvDesc()
-    d.in1 = a.data_ptr(); d.C1 = cin; d.ld1 = _ld(a); d.in2 = None; d.C2 = 0; d.ld2 = 0
-    d.N, d.H, d.W = n, h, w
-    d.w = wpk.data_ptr(); d.Kp = kp; d.kmode = kmode
-    d.bias = bgb.data_ptr(); d.res = None; d.ldr = 0
-    d.out = out.data_ptr(); d.Cout = o; d.ldo = _ld(out)
-    d.GH, d.GW, d.OH, d.OW = h, w, h, w
-    d.in_sy = d.in_sx = d.out_sy = d.out_sx = 1
-    d.out_oy = d.out_ox = 0
-    ops._fill_taps(d, taps)
-    d.act = ACT_NONE; d.slope = 0.0; d.bnpart = None; d.ws = None; d.ws_bytes = 0
+    d = ops._conv_desc(ops._at(a), cin, None, 0, (n, h, w), wpk.data_ptr(), kp, kmode, bgb, None, ops._at(out), o,
+                       (h, w, h, w), 1, 1, (0, 0), taps, ACT_NONE, 0.0)
     if not call('ssg_spade_conv_modulate_ok', C.byref(d)):
         return None
     gamma = new_nhwc(n, c, h, w, x.device)

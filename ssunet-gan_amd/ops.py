@@ -116,6 +116,25 @@ def bump_weight_epoch():
     _WEIGHT_EPOCH[0] += 1
 
 
+def _attach(t, name, value):
+    try:
+        setattr(t, name, value)
+    except Exception:                            # exotic tensor subclasses: just do not cache
+        pass
+    return value
+
+
+def _stamped_cache(t, name):
+    """The dict kept as attribute `name` ON tensor `t` (never keyed by address alone: a freed tensor's address can be reused by
+    another weight), as (stamp, dict).  It is valid for one (storage address, autograd version, optimizer epoch) of `t`: a new
+    stamp starts an empty dict."""
+    stamp = (t.data_ptr(), t._version, _WEIGHT_EPOCH[0])
+    cache = t.__dict__.get(name)
+    if cache is None or cache[0] != stamp:
+        cache = _attach(t, name, (stamp, {}))
+    return cache[1]
+
+
 def _pad4(pad):
     """int (symmetric) or (top, bottom, left, right) -> (pt, pb, pl, pr)."""
     if isinstance(pad, (tuple, list)):
@@ -143,26 +162,16 @@ def _pack(weight, transpose, taps, cred_pad, c1_for_mode, sigma=None):
         wc = weight.detach().contiguous()
         call('ssg_pack_weights_scaled_f32', ptr(wc), o, i, kh, kw, int(transpose), nt, ky, kx, kmode, cred_pad, kp, ptr(sigma), ptr(out), stream_ptr())
         return out, kp, kmode
-    # The cache lives ON the parameter object (never keyed by address alone: a freed tensor's
-    # address can be reused by another weight).  Entries are valid for one (storage address,
-    # autograd version, optimizer epoch) of that parameter.
-    stamp = (weight.data_ptr(), weight._version, _WEIGHT_EPOCH[0])
-    cache = weight.__dict__.get('_ssg_pack')
-    if cache is None or cache[0] != stamp:
-        cache = (stamp, {})
-        try:
-            weight._ssg_pack = cache
-        except Exception:                        # exotic tensor subclasses: just do not cache
-            pass
+    cache = _stamped_cache(weight, '_ssg_pack')
     key = (transpose, tuple(taps), cred_pad, kmode)
-    hit = cache[1].get(key)
+    hit = cache.get(key)
     if hit is not None:
         return hit, kp, kmode
     out = torch.empty((rows, kp), device=weight.device, dtype=torch.float32)
     ky = (C.c_int * nt)(*[t[0] for t in taps])
     kx = (C.c_int * nt)(*[t[1] for t in taps])
     call('ssg_pack_weights_f32', ptr(weight), o, i, kh, kw, int(transpose), nt, ky, kx, kmode, cred_pad, kp, ptr(out), stream_ptr())
-    cache[1][key] = out
+    cache[key] = out
     return out, kp, kmode
 
 
@@ -171,6 +180,53 @@ def _fill_taps(desc, taps):
     for t, (_, _, dy, dx) in enumerate(taps):
         desc.dy[t] = dy
         desc.dx[t] = dx
+
+
+def _at(t):
+    """(pointer, pixel stride) of an NHWC-with-stride tensor."""
+    return t.data_ptr(), _ld(t)
+
+
+def _conv_desc(in1, c1, in2, c2, nhw, w, kp, kmode, bias, res, out, cout, grid, in_s, out_s, out_o, taps, act, slope):
+    """ssg_conv_desc with the fields every launch sets.  in1 / in2 / res / out: (pointer, pixel stride) pairs (in2, res: or None);
+    c1 / c2, the pointers and `w` go in as given (padded counts and real pointers in _conv_launch, unpadded counts and stand-in
+    pointers in _x1_desc).  grid = (GH, GW, OH, OW).  Everything else (bnpart, ws, w_split, parity_merge, in_*, bwd_*) keeps the
+    structure's zero default for the caller that needs it."""
+    d = ConvDesc()
+    d.in1, d.ld1 = in1; d.C1 = c1
+    if in2 is not None:
+        d.in2, d.ld2 = in2; d.C2 = c2
+    d.N, d.H, d.W = nhw
+    d.w = w; d.Kp = kp; d.kmode = kmode
+    d.bias = bias.data_ptr() if bias is not None else None
+    if res is not None:
+        d.res, d.ldr = res
+    d.out, d.ldo = out; d.Cout = cout
+    d.GH, d.GW, d.OH, d.OW = grid
+    d.in_sy = d.in_sx = in_s
+    d.out_sy = d.out_sx = out_s
+    d.out_oy, d.out_ox = out_o
+    _fill_taps(d, taps)
+    d.act = act; d.slope = slope
+    return d
+
+
+def _wgrad_desc(x1, c1, x2, c2, dy, weight_shape, stride, taps):
+    """ssg_wgrad_desc of dW[weight_shape] from cat(x1, x2) and dy; c1 / c2 go in as given (padded for the fp32-class kernels,
+    unpadded for bf16x1).  flags, in_scale... and dw_oihw / ws are the caller's."""
+    o, i, kh, kw = weight_shape
+    d = WgradDesc()
+    d.in1, d.ld1 = _at(x1); d.C1 = c1
+    if x2 is not None:
+        d.in2, d.ld2 = _at(x2); d.C2 = c2
+    d.N, d.H, d.W = x1.shape[0], x1.shape[2], x1.shape[3]
+    d.dout, d.ldd = _at(dy); d.Cout = o; d.GH, d.GW = dy.shape[2], dy.shape[3]
+    d.in_sy = d.in_sx = stride
+    _fill_taps(d, taps)
+    for t, (ky, kx, _, _) in enumerate(taps):
+        d.ky[t] = ky; d.kx[t] = kx
+    d.KH, d.KW, d.Cin_real = kh, kw, i
+    return d
 
 
 # Optional per-launch timing (bench.py): a list that receives (kernel label, algorithmic FLOPs,
@@ -266,6 +322,26 @@ class _Timed(object):
             PROFILE.append((self.label, self.flops, self.e0, self.e1, self.tag))
 
 
+_CONV_SHAPE = ' n%d %dx%d cin%d cout%d taps%d s%d/%d'      # n, GH, GW, Cin, Cout, taps, in stride, out stride
+_WGRAD_SHAPE = ' n%d %dx%d cin%d cout%d k%d s%d'           # n, GH, GW, Cin, Cout, KH, stride
+# how a launch is named while profiling: (label table, entry point that returns the kernel id, PROFILE_SHAPES text)
+_CONV_KIND = (_CONV_LABELS, 'ssg_conv2d_kernel_id', _CONV_SHAPE)
+_WGRAD_KIND = (_WGRAD_LABELS, 'ssg_conv2d_wgrad_kernel_id', _WGRAD_SHAPE)
+
+
+def _timed_call(kind, entry, d, args, shape, flops, suffix='', tag=None):
+    """call(entry, &d, *args, stream): one MFMA launch.  While PROFILE is a list it is timed under its kernel's label + suffix
+    (+ the launch geometry `shape` under PROFILE_SHAPES); the id query is made only then."""
+    label = None
+    if PROFILE is not None:
+        labels, id_entry, shape_fmt = kind
+        label = labels.get(call(id_entry, C.byref(d)), '?') + suffix
+        if PROFILE_SHAPES:
+            label += shape_fmt % shape
+    with _Timed(label, flops, tag):
+        call(entry, C.byref(d), *args, stream_ptr())
+
+
 class _Declined(Exception):
     """_conv_launch: the library has no kernel for this parity-merged / in_affine / bwd_stats launch (nothing was allocated or launched)."""
 
@@ -279,32 +355,10 @@ def _conv_launch(x1, x2, wpk, kp, kmode, row0, cout, bias, res, act, slope, taps
     bwd_stats = (x, stats rows [mean, invstd, scale, shift], act, slope): the launch produces d(act(bn(x))), masks it and writes the
     batch-norm backward sums as per-tile rows (ssg_conv_desc.bwd_x).  Raises _Declined, with nothing allocated or launched, where
     the library has no kernel for a parity_merge / in_affine / bwd_stats launch."""
-    d = ConvDesc()
-    d.in1 = x1.data_ptr(); d.C1 = pad4(x1.shape[1]); d.ld1 = _ld(x1)
-    if x2 is not None:
-        d.in2 = x2.data_ptr(); d.C2 = pad4(x2.shape[1]); d.ld2 = _ld(x2)
-    else:
-        d.in2 = None; d.C2 = 0; d.ld2 = 0
-    d.N, d.H, d.W = n, h, w
-    d.w = wpk.data_ptr() + row0 * kp * 4; d.Kp = kp; d.kmode = kmode
-    d.bias = bias.data_ptr() if bias is not None else None
-    if res is not None:
-        d.res = res.data_ptr(); d.ldr = _ld(res)
-    else:
-        d.res = None; d.ldr = 0
-    d.out = out.data_ptr(); d.Cout = cout; d.ldo = _ld(out)
-    d.GH, d.GW, d.OH, d.OW = gh, gw, oh, ow
-    d.in_sy = d.in_sx = in_s
-    d.out_sy = d.out_sx = out_s
-    d.out_oy, d.out_ox = out_oy, out_ox
-    _fill_taps(d, taps)
-    d.act = act; d.slope = slope
-    d.bnpart = None
-    d.ws = None; d.ws_bytes = 0
-    d.w_split = None
+    d = _conv_desc(_at(x1), pad4(x1.shape[1]), _at(x2) if x2 is not None else None, pad4(x2.shape[1]) if x2 is not None else 0,
+                   (n, h, w), wpk.data_ptr() + row0 * kp * 4, kp, kmode, bias, _at(res) if res is not None else None, _at(out), cout,
+                   (gh, gw, oh, ow), in_s, out_s, (out_oy, out_ox), taps, act, slope)
     d.parity_merge = 1 if parity_merge else 0
-    d.in_scale = None; d.in_shift = None; d.in_act = ACT_NONE; d.in_slope = 0.0
-    d.bwd_x = None; d.bwd_ldx = 0; d.bwd_scale = None; d.bwd_shift = None; d.bwd_mean = None; d.bwd_act = ACT_NONE; d.bwd_slope = 0.0
     pack = call('ssg_conv2d_split_bn', C.byref(d)) if MFMA_SPLIT and kmode == 0 else 0
     if parity_merge and pack != 64:
         raise _Declined()
@@ -336,13 +390,8 @@ def _conv_launch(x1, x2, wpk, kp, kmode, row0, cout, bias, res, act, slope, taps
             ws = _ws(need, out.device)
             d.ws = ws.data_ptr(); d.ws_bytes = need
     cred = x1.shape[1] + (x2.shape[1] if x2 is not None else 0)
-    label = None
-    if PROFILE is not None:
-        label = _CONV_LABELS.get(call('ssg_conv2d_kernel_id', C.byref(d)), '?') + ('+splitk' if ws is not None else '')
-        if PROFILE_SHAPES:
-            label += ' n%d %dx%d cin%d cout%d taps%d s%d/%d' % (n, gh, gw, cred, cout, len(taps), in_s, out_s)
-    with _Timed(label, 2.0 * n * gh * gw * cout * cred * len(taps), tag):
-        call('ssg_conv2d_f32', C.byref(d), stream_ptr())
+    _timed_call(_CONV_KIND, 'ssg_conv2d_f32', d, (), (n, gh, gw, cred, cout, len(taps), in_s, out_s),
+                2.0 * n * gh * gw * cout * cred * len(taps), '+splitk' if ws is not None else '', tag)
     return part
 
 
@@ -365,11 +414,7 @@ def _split_pack(wpk, row0, rows, kp, bn):
     tensor, which itself lives in the parameter's pack cache: both go stale together)."""
     cache = wpk.__dict__.get('_ssg_split')
     if cache is None:
-        cache = {}
-        try:
-            wpk._ssg_split = cache
-        except Exception:
-            pass
+        cache = _attach(wpk, '_ssg_split', {})
     key = (row0, rows, bn)
     hit = cache.get(key)
     if hit is None:
@@ -389,10 +434,28 @@ def _out_hw(h, w, kh, kw, s, pad):
     return (h + pt + pb - kh) // s + 1, (w + pl + pr - kw) // s + 1
 
 
-def _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=None, out=None, wscale=None, want_bn=False, in_affine=None):
+def _x1_routed(precision, stride, pad, wscale, fused):
+    """True where a conv call under `precision` asks the bf16x1 kernels first: 'bf16x1' and a unit-stride pad-1 conv of unscaled
+    weights (the 3x3 window and the shapes are the launchers' own predicates).  `fused` (in_affine / bwd_stats) has no bf16x1
+    form: the combination is refused."""
+    if precision == 'fp32':
+        return False
+    if precision != 'bf16x1':
+        raise ValueError('conv: unknown precision %r (one of %s)' % (precision, ', '.join(_PRECISIONS)))
+    if fused is not None:
+        raise ValueError("conv: in_affine / bwd_stats cannot be combined with precision='bf16x1'")
+    return stride == 1 and _pad4(pad) == (1, 1, 1, 1) and wscale is None
+
+
+def _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=None, out=None, wscale=None, want_bn=False, in_affine=None, precision='fp32'):
     """Returns y, or (y, part) with want_bn: part = per-tile batch-norm partial sums of y from the conv epilogue, or None when
     the kernel this shape maps to has none (the batch norm then runs its own statistics pass).  in_affine: see _conv_launch; the
-    result is None (nothing launched) when the library declines."""
+    result is None (nothing launched) when the library declines.  precision='bf16x1': a unit-stride 3x3 pad-1 conv runs on
+    _conv_bf16x1_impl where conv2d_bf16x1_ok holds (part is then None: that launcher has no statistics epilogue) and on the
+    fp32-class kernel below where it refuses."""
+    if _x1_routed(precision, stride, pad, wscale, in_affine) and conv2d_bf16x1_ok(x1, weight, x2=x2, res=res):
+        y = _conv_bf16x1_impl(x1, weight, bias, act, slope, x2=x2, res=res, out=out)
+        return (y, None) if want_bn else y
     o, i, kh, kw = weight.shape
     n, c1, h, w = x1.shape
     c2 = x2.shape[1] if x2 is not None else 0
@@ -415,12 +478,17 @@ def _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=None, out=
     return (out, part) if want_bn else out
 
 
-def _conv_dgrad_impl(dy, weight, stride, pad, h, w, c_lo, c_hi, res=None, wscale=None, bwd_stats=None):
+def _conv_dgrad_impl(dy, weight, stride, pad, h, w, c_lo, c_hi, res=None, wscale=None, bwd_stats=None, precision='fp32'):
     """Input gradient for input channels [c_lo, c_hi) -> NHWC tensor [N, c_hi-c_lo, h, w].
     `res` (same shape) is added in the epilogue: gradient accumulation without an extra pass.
     bwd_stats = (x, stats, act, slope): the gradient is that of act(bn(x)); returns (g, part) -- the MASKED gradient and the per-tile rows
     (sum g, sum g * (x - mean)) of the batch-norm backward from the epilogue (ssg_conv_desc.bwd_x) -- or None, with nothing launched,
-    where the kernel this launch maps to has no such epilogue."""
+    where the kernel this launch maps to has no such epilogue.  precision='bf16x1': a unit-stride 3x3 pad-1 gradient is
+    _conv_dgrad_bf16x1_impl's where that takes it, and the fp32-class kernel's below where it refuses."""
+    if _x1_routed(precision, stride, pad, wscale, bwd_stats):
+        dx = _conv_dgrad_bf16x1_impl(dy, weight, h, w, c_lo, c_hi, res=res)
+        if dx is not None:
+            return dx
     o, i, kh, kw = weight.shape
     n, _, oh, ow = dy.shape
     cred_pad = pad4(o)
@@ -474,31 +542,22 @@ def _conv_dgrad_impl(dy, weight, stride, pad, h, w, c_lo, c_hi, res=None, wscale
     return dx
 
 
-def _conv_wgrad_impl(x1, x2, dy, weight_shape, stride, pad, in_affine=None):
+def _conv_wgrad_impl(x1, x2, dy, weight_shape, stride, pad, in_affine=None, precision='fp32'):
     """in_affine = (scale, shift, act, slope): the x operand is act(x1 * scale + shift) (ssg_wgrad_desc.in_scale); returns None,
-    with nothing launched, when the kernel this shape maps to has no such transform."""
+    with nothing launched, when the kernel this shape maps to has no such transform.  precision='bf16x1': a unit-stride 3x3 pad-1
+    weight gradient is _conv_wgrad_bf16x1_impl's where that takes it, and the fp32-class kernel's below where it refuses."""
+    if _x1_routed(precision, stride, pad, None, in_affine):
+        dw = _conv_wgrad_bf16x1_impl(x1, x2, dy, weight_shape)
+        if dw is not None:
+            return dw
     o, i, kh, kw = weight_shape
-    n, c1, h, w = x1.shape
+    n = x1.shape[0]
     _, _, oh, ow = dy.shape
-    d = WgradDesc()
-    d.in1 = x1.data_ptr(); d.C1 = pad4(c1); d.ld1 = _ld(x1)
-    if x2 is not None:
-        d.in2 = x2.data_ptr(); d.C2 = pad4(x2.shape[1]); d.ld2 = _ld(x2)
-    else:
-        d.in2 = None; d.C2 = 0; d.ld2 = 0
-    d.N, d.H, d.W = n, h, w
-    d.dout = dy.data_ptr(); d.Cout = o; d.ldd = _ld(dy); d.GH, d.GW = oh, ow
-    d.in_sy = d.in_sx = stride
-    taps = _taps_fwd(kh, kw, pad)
-    _fill_taps(d, taps)
-    for t, (ky, kx, _, _) in enumerate(taps):
-        d.ky[t] = ky; d.kx[t] = kx
-    d.KH, d.KW, d.Cin_real = kh, kw, i
+    d = _wgrad_desc(x1, pad4(x1.shape[1]), x2, pad4(x2.shape[1]) if x2 is not None else 0, dy, weight_shape, stride,
+                    _taps_fwd(kh, kw, pad))
     dw = torch.empty((o, i, kh, kw), device=dy.device, dtype=torch.float32)
     d.dw_oihw = dw.data_ptr()
-    d.ws = None; d.ws_bytes = 0
     d.flags = 1 if MFMA_SPLIT else 0
-    d.in_scale = None; d.in_shift = None; d.in_act = ACT_NONE; d.in_slope = 0.0
     if in_affine is not None:
         d.in_scale = in_affine[0].data_ptr(); d.in_shift = in_affine[1].data_ptr(); d.in_act = int(in_affine[2]); d.in_slope = float(in_affine[3])
         if not call('ssg_conv2d_wgrad_in_affine_ok', C.byref(d)):
@@ -506,13 +565,7 @@ def _conv_wgrad_impl(x1, x2, dy, weight_shape, stride, pad, in_affine=None):
     nbytes = call('ssg_conv2d_wgrad_workspace_bytes', C.byref(d))
     ws = _ws(nbytes, dy.device)
     d.ws = ws.data_ptr(); d.ws_bytes = ws.numel() * 8
-    label = None
-    if PROFILE is not None:
-        label = _WGRAD_LABELS.get(call('ssg_conv2d_wgrad_kernel_id', C.byref(d)), '?')
-        if PROFILE_SHAPES:
-            label += ' n%d %dx%d cin%d cout%d k%d s%d' % (n, oh, ow, i, o, kh, stride)
-    with _Timed(label, 2.0 * n * oh * ow * o * i * kh * kw):
-        call('ssg_conv2d_wgrad_f32', C.byref(d), stream_ptr())
+    _timed_call(_WGRAD_KIND, 'ssg_conv2d_wgrad_f32', d, (), (n, oh, ow, i, o, kh, stride), 2.0 * n * oh * ow * o * i * kh * kw)
     return dw
 
 
@@ -533,17 +586,18 @@ def _act_bwd(y, dy, act, slope):
 
 
 class _Conv2d(torch.autograd.Function):
-    """F.conv2d (+bias, +activation, optional second input = channel concat) on MFMA."""
+    """F.conv2d (+bias, +activation, optional second input = channel concat) on MFMA.  `precision` (see _conv_fwd_impl) is the
+    forward's and, kept on ctx, that of the three gradients."""
 
     @staticmethod
-    def forward(ctx, x1, x2, weight, bias, stride, pad, act, slope, res=None, want_bn=False):
+    def forward(ctx, x1, x2, weight, bias, stride, pad, act, slope, res=None, want_bn=False, precision='fp32'):
         ctx.set_materialize_grads(False)       # no zero tensor for the (non-differentiable) statistics output's gradient
         x1 = to_nhwc(x1)
         x2 = to_nhwc(x2) if x2 is not None else None
         res = to_nhwc(res) if res is not None else None
-        y, part = _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=res, want_bn=True) if want_bn else \
-            (_conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=res), None)
-        ctx.cfg = (stride, pad, act, slope)
+        r = _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=res, want_bn=want_bn, precision=precision)
+        y, part = r if want_bn else (r, None)
+        ctx.cfg = (stride, pad, act, slope, precision)
         ctx.save_for_backward(x1, x2, weight, y if act != ACT_NONE else None)
         ctx.has_bias = bias is not None
         ctx.has_res = res is not None
@@ -556,24 +610,24 @@ class _Conv2d(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy, _=None):
         if dy is None:
-            return (None,) * 10
+            return (None,) * 11
         x1, x2, weight, y = ctx.saved_tensors
-        stride, pad, act, slope = ctx.cfg
+        stride, pad, act, slope, precision = ctx.cfg
         dy = to_nhwc(dy)
         if act != ACT_NONE:
             dy = _act_bwd(y, dy, act, slope)
         n, c1, h, w = x1.shape
         dx1 = dx2 = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx1 = _conv_dgrad_impl(dy, weight, stride, pad, h, w, 0, c1)
+            dx1 = _conv_dgrad_impl(dy, weight, stride, pad, h, w, 0, c1, precision=precision)
         if x2 is not None and ctx.needs_input_grad[1]:
-            dx2 = _conv_dgrad_impl(dy, weight, stride, pad, h, w, c1, c1 + x2.shape[1])
+            dx2 = _conv_dgrad_impl(dy, weight, stride, pad, h, w, c1, c1 + x2.shape[1], precision=precision)
         if ctx.needs_input_grad[2]:
-            dw = _conv_wgrad_impl(x1, x2, dy, weight.shape, stride, pad)
+            dw = _conv_wgrad_impl(x1, x2, dy, weight.shape, stride, pad, precision=precision)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             db = _channel_sum(dy, weight.shape[0])
         dres = dy if (ctx.has_res and ctx.needs_input_grad[8]) else None      # residual joins before the activation
-        return dx1, dx2, dw, db, None, None, None, None, dres, None
+        return dx1, dx2, dw, db, None, None, None, None, dres, None, None
 
 
 def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, x2=None, res=None, bn_stats=False):
@@ -584,7 +638,7 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, x
     this shape's kernel has none); hand it to batch_norm_act(y, bn, stats_part=part) to skip its statistics pass."""
     _lib.require_gpu(x)
     pad = tuple(int(v) for v in padding) if isinstance(padding, (tuple, list)) else int(padding)
-    y, part = _Conv2d.apply(x, x2, weight, bias, int(stride), pad, int(act), float(slope), res, bool(bn_stats))
+    y, part = _Conv2d.apply(x, x2, weight, bias, int(stride), pad, int(act), float(slope), res, bool(bn_stats), 'fp32')
     return (y, part) if bn_stats else y
 
 
@@ -593,34 +647,39 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, x
 # (ssg_conv2d_bf16x1_f32).  An approximation, forward only, chosen per call: nothing here is reached from a training path, and
 # ops.conv2d never routes to it.
 _X1_LABELS = {70: 'conv_halo_k32_x1_kernel<128>', 71: 'conv_halo_k32_x1_kernel<64>'}
+_X1_KIND = (_X1_LABELS, 'ssg_conv2d_bf16x1_kernel_id', _CONV_SHAPE)
 _X1_TAPS = _taps_fwd(3, 3, 1)
-_INFER_PRECISIONS = ('fp32', 'bf16x1')
-_INFER_PRECISION = ['fp32']
+_PRECISIONS = ('fp32', 'bf16x1')
 
 
-class infer_precision(object):
+class _precision(object):
+    """Base of infer_precision / train_precision: a nestable context that sets its own class's mode (`_state`)."""
+
+    def __init__(self, mode):
+        if mode not in _PRECISIONS:
+            raise ValueError('%s: unknown mode %r (one of %s)' % (type(self).__name__, mode, ', '.join(_PRECISIONS)))
+        self.mode = mode
+
+    def __enter__(self):
+        self.prev = self._state[0]; self._state[0] = self.mode
+        return self
+
+    def __exit__(self, *a):
+        self._state[0] = self.prev
+
+
+class infer_precision(_precision):
     """with ops.infer_precision('bf16x1'): ...   -- eval-mode modules (archs.BasicBlock) run their 3x3 stride-1 convs on
     conv2d_bf16x1 where conv2d_bf16x1_ok holds (bf16 operand rounding, fp32 accumulation: an approximation) and stay on conv2d
     elsewhere.  'fp32' (the default) is today's behaviour.  Read by eval-mode module code under torch.no_grad() only: a forward
     that records a graph (autograd enabled and something requires grad) runs the fp32-class kernels whatever the mode says, and so
     does every training path."""
-
-    def __init__(self, mode):
-        if mode not in _INFER_PRECISIONS:
-            raise ValueError('infer_precision: unknown mode %r (one of %s)' % (mode, ', '.join(_INFER_PRECISIONS)))
-        self.mode = mode
-
-    def __enter__(self):
-        self.prev = _INFER_PRECISION[0]; _INFER_PRECISION[0] = self.mode
-        return self
-
-    def __exit__(self, *a):
-        _INFER_PRECISION[0] = self.prev
+    _state = ['fp32']
 
 
 def infer_precision_mode():
     """The mode the innermost `infer_precision` block set ('fp32' outside any)."""
-    return _INFER_PRECISION[0]
+    return infer_precision._state[0]
 
 
 def _x1_desc(x, x2, weight, res, out=None):
@@ -630,30 +689,11 @@ def _x1_desc(x, x2, weight, res, out=None):
         ld = nhwc_ld(t)
         return (t.data_ptr(), ld) if ld is not None else (16, pad4(t.shape[1]))
     n, c1, h, w = x.shape
-    d = ConvDesc()
-    d.in1, d.ld1 = side(x); d.C1 = c1
-    if x2 is not None:
-        d.in2, d.ld2 = side(x2); d.C2 = x2.shape[1]
-    else:
-        d.in2 = None; d.C2 = 0; d.ld2 = 0
-    d.N, d.H, d.W = n, h, w
-    d.w = 16; d.Kp = 9 * (d.C1 + d.C2); d.kmode = 0
-    d.bias = None
-    if res is not None:
-        d.res, d.ldr = side(res)
-    else:
-        d.res = None; d.ldr = 0
-    d.Cout = weight.shape[0]
-    d.out, d.ldo = side(out) if out is not None else (16, pad4(d.Cout))
-    d.GH, d.GW, d.OH, d.OW = h, w, h, w
-    d.in_sy = d.in_sx = d.out_sy = d.out_sx = 1
-    d.out_oy = d.out_ox = 0
-    _fill_taps(d, _X1_TAPS)
-    d.act = ACT_NONE; d.slope = 0.0
-    d.bnpart = None; d.ws = None; d.ws_bytes = 0; d.w_split = None; d.parity_merge = 0
-    d.in_scale = None; d.in_shift = None; d.in_act = ACT_NONE; d.in_slope = 0.0
-    d.bwd_x = None; d.bwd_ldx = 0; d.bwd_scale = None; d.bwd_shift = None; d.bwd_mean = None; d.bwd_act = ACT_NONE; d.bwd_slope = 0.0
-    return d
+    c2 = x2.shape[1] if x2 is not None else 0
+    o = weight.shape[0]
+    return _conv_desc(side(x), c1, side(x2) if x2 is not None else None, c2, (n, h, w), 16, 9 * (c1 + c2), 0, None,
+                      side(res) if res is not None else None, side(out) if out is not None else (16, pad4(o)), o,
+                      (h, w, h, w), 1, 1, (0, 0), _X1_TAPS, ACT_NONE, 0.0)
 
 
 def _x1_shapes_ok(x, weight, x2, res):
@@ -677,23 +717,16 @@ def _x1_pack(weight, wpk, kp, fmt, transpose=0, row0=0, rows=None):
     """The bf16 pack of `weight` (OIHW) for format `fmt`, built from its fp32 kmode-0 matrix `wpk`; cached on the weight tensor as
     `_ssg_pack_bf16x1`, stamped like `_ssg_pack`.  transpose / row0 / rows: rows [row0, row0 + rows) of the TRANSPOSED matrix (an
     input gradient for a channel slice of a concat input); such packs are keyed (transpose, row0, rows, fmt)."""
-    stamp = (weight.data_ptr(), weight._version, _WEIGHT_EPOCH[0])
-    cache = weight.__dict__.get('_ssg_pack_bf16x1')
-    if cache is None or cache[0] != stamp:
-        cache = (stamp, {})
-        try:
-            weight._ssg_pack_bf16x1 = cache
-        except Exception:
-            pass
+    cache = _stamped_cache(weight, '_ssg_pack_bf16x1')
     if rows is None:
         rows = weight.shape[0]
     key = (transpose, row0, rows, fmt) if transpose else fmt
-    hit = cache[1].get(key)
+    hit = cache.get(key)
     if hit is None:
         nbytes = call('ssg_pack_weights_bf16x1_bytes', rows, kp, fmt)
         hit = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
         call('ssg_pack_weights_bf16x1', wpk.data_ptr() + row0 * kp * 4, rows, kp, fmt, ptr(hit), stream_ptr())
-        cache[1][key] = hit
+        cache[key] = hit
     return hit
 
 
@@ -715,13 +748,8 @@ def _conv_bf16x1_impl(x, weight, bias, act, slope, x2=None, res=None, out=None):
     if not fmt:
         call('ssg_conv2d_bf16x1_f32', C.byref(d), None, stream_ptr())      # refused on the host, nothing launched: raises with the reason
     pack = _x1_pack(weight, wpk, kp, fmt)
-    label = None
-    if PROFILE is not None:
-        label = _X1_LABELS.get(call('ssg_conv2d_bf16x1_kernel_id', C.byref(d)), '?')
-        if PROFILE_SHAPES:
-            label += ' n%d %dx%d cin%d cout%d taps9 s1/1' % (n, h, w, weight.shape[1], o)
-    with _Timed(label, 2.0 * n * h * w * o * weight.shape[1] * 9, _ROLE[0]):
-        call('ssg_conv2d_bf16x1_f32', C.byref(d), ptr(pack), stream_ptr())
+    _timed_call(_X1_KIND, 'ssg_conv2d_bf16x1_f32', d, (ptr(pack),), (n, h, w, weight.shape[1], o, 9, 1, 1),
+                2.0 * n * h * w * o * weight.shape[1] * 9, tag=_ROLE[0])
     return out
 
 
@@ -746,59 +774,24 @@ def conv2d_bf16x1(x, weight, bias=None, act=ACT_NONE, slope=0.0, x2=None, res=No
 # 'fp32 master weights, bf16 operands, fp32 accumulation' for the dense 3x3 stride-1 convs: forward and input gradient on
 # conv_halo_k32_x1_kernel (the input gradient is the same convolution on dy with the transposed pack and the taps (1 - ky, 1 - kx)),
 # weight gradient on wgrad_k32_x1_kernel (csrc/conv_wgrad_k32_x1.hip).  Every tensor in HBM stays fp32.  Chosen by the caller:
-# ops.conv2d and its autograd node never come here.
+# ops.conv2d never comes here.
 _WGRAD_X1_LABELS = {72: 'wgrad_k32_x1_kernel'}
+_WGRAD_X1_KIND = (_WGRAD_X1_LABELS, 'ssg_conv2d_wgrad_bf16x1_kernel_id', _WGRAD_SHAPE)
 _X1_TAPS_T = [(ky, kx, 1 - ky, 1 - kx) for ky in range(3) for kx in range(3)]
-_TRAIN_PRECISIONS = ('fp32', 'bf16x1')
-_TRAIN_PRECISION = ['fp32']
 
 
-class train_precision(object):
+class train_precision(_precision):
     """with ops.train_precision('bf16x1'): ...   -- autograd nodes that have a bf16x1 route (blocks._BasicBlockFn,
     blocks._FrozenBasicBlockFn) run their 3x3 stride-1 convs, forward, input gradient and weight gradient, with both operands
     rounded once to bf16 (fp32 accumulation, fp32 tensors: an approximation) wherever the kernels' predicates hold, and stay on the
     fp32-class kernels elsewhere.  'fp32' (the default) launches exactly what runs without the context.  A node reads the mode in
     its forward and keeps it: its backward uses the forward's mode whatever is set when .backward() runs."""
-
-    def __init__(self, mode):
-        if mode not in _TRAIN_PRECISIONS:
-            raise ValueError('train_precision: unknown mode %r (one of %s)' % (mode, ', '.join(_TRAIN_PRECISIONS)))
-        self.mode = mode
-
-    def __enter__(self):
-        self.prev = _TRAIN_PRECISION[0]; _TRAIN_PRECISION[0] = self.mode
-        return self
-
-    def __exit__(self, *a):
-        _TRAIN_PRECISION[0] = self.prev
+    _state = ['fp32']
 
 
 def train_precision_mode():
     """The mode the innermost `train_precision` block set ('fp32' outside any)."""
-    return _TRAIN_PRECISION[0]
-
-
-def _wgrad_x1_desc(x1, x2, dy, weight_shape):
-    o, i, kh, kw = weight_shape
-    n, c1, h, w = x1.shape
-    d = WgradDesc()
-    d.in1 = x1.data_ptr(); d.C1 = c1; d.ld1 = _ld(x1)
-    if x2 is not None:
-        d.in2 = x2.data_ptr(); d.C2 = x2.shape[1]; d.ld2 = _ld(x2)
-    else:
-        d.in2 = None; d.C2 = 0; d.ld2 = 0
-    d.N, d.H, d.W = n, h, w
-    d.dout = dy.data_ptr(); d.Cout = o; d.ldd = _ld(dy); d.GH, d.GW = dy.shape[2], dy.shape[3]
-    d.in_sy = d.in_sx = 1
-    _fill_taps(d, _X1_TAPS)
-    for t, (ky, kx, _, _) in enumerate(_X1_TAPS):
-        d.ky[t] = ky; d.kx[t] = kx
-    d.KH, d.KW, d.Cin_real = kh, kw, i
-    d.dw_oihw = None
-    d.ws = None; d.ws_bytes = 0
-    d.flags = 0
-    d.in_scale = None; d.in_shift = None; d.in_act = ACT_NONE; d.in_slope = 0.0
-    return d
+    return train_precision._state[0]
 
 
 def _conv_wgrad_bf16x1_impl(x1, x2, dy, weight_shape):
@@ -808,7 +801,7 @@ def _conv_wgrad_bf16x1_impl(x1, x2, dy, weight_shape):
     o, i, kh, kw = weight_shape
     if (kh, kw) != (3, 3) or tuple(dy.shape[2:]) != tuple(x1.shape[2:]) or x1.shape[1] + (x2.shape[1] if x2 is not None else 0) != i:
         return None
-    d = _wgrad_x1_desc(x1, x2, dy, weight_shape)
+    d = _wgrad_desc(x1, x1.shape[1], x2, x2.shape[1] if x2 is not None else 0, dy, weight_shape, 1, _X1_TAPS)
     if not call('ssg_conv2d_wgrad_bf16x1_ok', C.byref(d)):
         return None
     n, _, h, w = x1.shape
@@ -816,13 +809,7 @@ def _conv_wgrad_bf16x1_impl(x1, x2, dy, weight_shape):
     d.dw_oihw = dw.data_ptr()
     ws = _ws(call('ssg_conv2d_wgrad_bf16x1_workspace_bytes', C.byref(d)), dy.device)
     d.ws = ws.data_ptr(); d.ws_bytes = ws.numel() * 8
-    label = None
-    if PROFILE is not None:
-        label = _WGRAD_X1_LABELS.get(call('ssg_conv2d_wgrad_bf16x1_kernel_id', C.byref(d)), '?')
-        if PROFILE_SHAPES:
-            label += ' n%d %dx%d cin%d cout%d k3 s1' % (n, h, w, i, o)
-    with _Timed(label, 2.0 * n * h * w * o * i * 9):
-        call('ssg_conv2d_wgrad_bf16x1_f32', C.byref(d), stream_ptr())
+    _timed_call(_WGRAD_X1_KIND, 'ssg_conv2d_wgrad_bf16x1_f32', d, (), (n, h, w, i, o, 3, 1), 2.0 * n * h * w * o * i * 9)
     return dw
 
 
@@ -849,63 +836,8 @@ def _conv_dgrad_bf16x1_impl(dy, weight, h, w, c_lo, c_hi, res=None):
     if not fmt:
         return None
     pack = _x1_pack(weight, wpk, kp, fmt, transpose=1, row0=c_lo, rows=rows)
-    label = None
-    if PROFILE is not None:
-        label = _X1_LABELS.get(call('ssg_conv2d_bf16x1_kernel_id', C.byref(d)), '?')
-        if PROFILE_SHAPES:
-            label += ' n%d %dx%d cin%d cout%d taps9 s1/1' % (n, h, w, o, rows)
-    with _Timed(label, 2.0 * n * h * w * o * rows * 9):
-        call('ssg_conv2d_bf16x1_f32', C.byref(d), ptr(pack), stream_ptr())
+    _timed_call(_X1_KIND, 'ssg_conv2d_bf16x1_f32', d, (ptr(pack),), (n, h, w, o, rows, 9, 1, 1), 2.0 * n * h * w * o * rows * 9)
     return dx
-
-
-def _conv_bwd_bf16x1(x1, x2, weight, dy, need_x1, need_x2, need_w):
-    """The three gradients of a routed 3x3 conv under train_precision('bf16x1'): each on the bf16x1 kernel where its predicate
-    holds, on the fp32-class kernel for that one launch where it refuses."""
-    n, c1, h, w = x1.shape
-    dx1 = dx2 = dw = None
-    if need_x1:
-        dx1 = _conv_dgrad_bf16x1_impl(dy, weight, h, w, 0, c1)
-        if dx1 is None:
-            dx1 = _conv_dgrad_impl(dy, weight, 1, 1, h, w, 0, c1)
-    if x2 is not None and need_x2:
-        dx2 = _conv_dgrad_bf16x1_impl(dy, weight, h, w, c1, c1 + x2.shape[1])
-        if dx2 is None:
-            dx2 = _conv_dgrad_impl(dy, weight, 1, 1, h, w, c1, c1 + x2.shape[1])
-    if need_w:
-        dw = _conv_wgrad_bf16x1_impl(x1, x2, dy, weight.shape)
-        if dw is None:
-            dw = _conv_wgrad_impl(x1, x2, dy, weight.shape, 1, 1)
-    return dx1, dx2, dw
-
-
-class _Conv2dBf16x1(torch.autograd.Function):
-    """conv2d_bf16x1_train: act(conv3x3(cat(x, x2)) + bias + res), all three directions on the one-term bf16 kernels."""
-
-    @staticmethod
-    def forward(ctx, x1, x2, weight, bias, act, slope, res):
-        x1 = to_nhwc(x1)
-        x2 = to_nhwc(x2) if x2 is not None else None
-        res = to_nhwc(res) if res is not None else None
-        y = _conv_bf16x1_impl(x1, weight, bias, act, slope, x2=x2, res=res)
-        ctx.cfg = (act, slope)
-        ctx.save_for_backward(x1, x2, weight, y if act != ACT_NONE else None)
-        ctx.has_bias = bias is not None
-        ctx.has_res = res is not None
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        x1, x2, weight, y = ctx.saved_tensors
-        act, slope = ctx.cfg
-        dy = to_nhwc(dy)
-        if act != ACT_NONE:
-            dy = _act_bwd(y, dy, act, slope)
-        dx1, dx2, dw = _conv_bwd_bf16x1(x1, x2, weight, dy, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2])
-        db = _channel_sum(dy, weight.shape[0]) if (ctx.has_bias and ctx.needs_input_grad[3]) else None
-        dres = dy if (ctx.has_res and ctx.needs_input_grad[6]) else None      # residual joins before the activation
-        return dx1, dx2, dw, db, None, None, dres
 
 
 def conv2d_bf16x1_train(x, weight, bias=None, act=ACT_NONE, slope=0.0, x2=None, res=None):
@@ -919,7 +851,7 @@ def conv2d_bf16x1_train(x, weight, bias=None, act=ACT_NONE, slope=0.0, x2=None, 
     if not conv2d_bf16x1_ok(x, weight, x2=x2, res=res):
         raise ValueError('conv2d_bf16x1_train: no bf16x1 kernel for x %s x2 %s weight %s res %s (conv2d_bf16x1_ok is False)' % (
             tuple(x.shape), None if x2 is None else tuple(x2.shape), tuple(weight.shape), None if res is None else tuple(res.shape)))
-    return _Conv2dBf16x1.apply(x, x2, weight, bias, int(act), float(slope), res)
+    return _Conv2d.apply(x, x2, weight, bias, 1, 1, int(act), float(slope), res, False, 'bf16x1')[0]
 
 
 # ----------------------------------------------------------------------------- linear (as 1x1 conv over a 1 x N "image")

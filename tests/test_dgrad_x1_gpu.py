@@ -5,7 +5,8 @@ weight rounded once to bf16, fp32 accumulation), at the small shapes of tests/te
 Gates: integer operands in [-3, 3] -> bit equality with fp64; full-mantissa operands -> against fp64 on the rounded operands
 (K + 2) u32 mag + u32 |ref| (K = 9 Cout products per element, one more term for the residual, any summation order), and against
 fp64 on the operands as given that plus (2^-8 + 2^-18) sum |dy| |w|.  Where the predicate refuses (a 32-channel slice, a
-16-pixel-wide image) the launcher returns None with nothing launched, and blocks._dgrad3 runs _conv_dgrad_impl, bit for bit."""
+16-pixel-wide image) the launcher returns None with nothing launched, and _conv_dgrad_impl(precision='bf16x1') runs its
+fp32-class kernel, bit for bit."""
 import numpy as np
 import pytest
 import torch
@@ -107,7 +108,7 @@ def test_pack_is_cached_per_slice(pkg, dev):
 
 @pytest.mark.parametrize('shape', [(1, 64, 64, 4, 40, 0, 32), (1, 64, 64, 4, 16, 0, 64)], ids=['slice32', 'w16'])
 def test_refused_launch_falls_back_to_the_fp32_class_kernel(pkg, dev, shape):
-    ops, blocks = pkg.ops, pkg.blocks
+    ops = pkg.ops
     n, o, i, h, w, lo, hi = shape
     g = torch.Generator().manual_seed(3)
     dy = ops.to_nhwc(torch.randn(n, o, h, w, generator=g).to(dev)); wd = torch.randn(o, i, 3, 3, generator=g).to(dev)
@@ -115,7 +116,7 @@ def test_refused_launch_falls_back_to_the_fp32_class_kernel(pkg, dev, shape):
     try:
         assert ops._conv_dgrad_bf16x1_impl(dy, wd, h, w, lo, hi) is None
         assert ops.PROFILE == [], 'a refused launcher launched something'
-        got = blocks._dgrad3(True, dy, wd, h, w, lo, hi)
+        got = ops._conv_dgrad_impl(dy, wd, 1, 1, h, w, lo, hi, precision='bf16x1')
         labels = [r[0] for r in ops.PROFILE]
     finally:
         ops.PROFILE = None
