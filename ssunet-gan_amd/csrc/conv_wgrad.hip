@@ -285,6 +285,22 @@ bool in_affine_ok(const ssg_wgrad_desc* d, const Plan& p) {
   return p.kind == WG_K32;
 }
 
+// the kernels' argument block of a validated descriptor under plan p
+WgArgs wgrad_args(const ssg_wgrad_desc* d, const Plan& p) {
+  WgArgs a;
+  a.in1 = d->in1; a.in2 = d->C2 ? d->in2 : d->in1; a.dout = d->dout; a.ws = d->ws;
+  a.C1 = d->C1; a.C2 = d->C2; a.ld1 = d->ld1; a.ld2 = d->C2 ? d->ld2 : d->ld1;
+  a.N = d->N; a.H = d->H; a.W = d->W; a.Cout = d->Cout; a.ldd = d->ldd; a.GH = d->GH; a.GW = d->GW;
+  a.in_sy = d->in_sy; a.in_sx = d->in_sx; a.ntaps = d->ntaps;
+  a.tap_bits = ssg_pack_taps(d->dy, d->dx, d->ntaps);
+  a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.in_act = d->in_act; a.in_slope = d->in_slope;
+  a.M = d->ntaps * (d->C1 + d->C2);
+  a.Ptot = (long long)d->N * d->GH * d->GW;
+  a.steps_per_split = p.steps_per_split;
+  a.xcd_swizzle = 0;
+  return a;
+}
+
 __global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restrict__ w, int O, int I, int KH, int KW,
                                                            int transpose, int ntaps, unsigned long long kpos_bits,
                                                            int kmode, int Cred_pad, int Kp, int R, float* __restrict__ out,
@@ -331,16 +347,7 @@ extern "C" int ssg_conv2d_wgrad_f32(const ssg_wgrad_desc* d, void* stream) {
   SSG_REQUIRE(!d->in_scale || (d->in_shift && in_affine_ok(d, p)), SSG_EINVAL,
               "wgrad: in_scale on a descriptor whose kernel has no fused input transform (ssg_conv2d_wgrad_in_affine_ok == 0)");
   hipStream_t st = (hipStream_t)stream;
-  WgArgs a;
-  a.in1 = d->in1; a.in2 = d->C2 ? d->in2 : d->in1; a.dout = d->dout; a.ws = d->ws;
-  a.C1 = d->C1; a.C2 = d->C2; a.ld1 = d->ld1; a.ld2 = d->C2 ? d->ld2 : d->ld1;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cout = d->Cout; a.ldd = d->ldd; a.GH = d->GH; a.GW = d->GW;
-  a.in_sy = d->in_sy; a.in_sx = d->in_sx; a.ntaps = d->ntaps;
-  a.tap_bits = ssg_pack_taps(d->dy, d->dx, d->ntaps);
-  a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.in_act = d->in_act; a.in_slope = d->in_slope;
-  a.M = d->ntaps * (d->C1 + d->C2);
-  a.Ptot = (long long)d->N * d->GH * d->GW;
-  a.steps_per_split = p.steps_per_split;
+  WgArgs a = wgrad_args(d, p);
   if (p.kind == WG_4) {
     rc = ssg_wgrad4_launch(d, p.variant, st);
     if (rc != SSG_OK) return rc;
@@ -429,4 +436,14 @@ extern "C" int ssg_conv2d_wgrad_kernel_id(const ssg_wgrad_desc* d) {
   if (p.kind == WG_K32) return 60;
   if (p.kind == WG_HALO) return ((d->flags & 1) ? 40 : 30) + p.variant;
   return p.variant + (wgrad_uses_dma(p.variant) ? ((d->flags & 1) ? 50 : 20) : 0);
+}
+
+// Diagnostic, outside the ABI of include/ssunet_hip.h (tests/test_wgrad_dma_split_once_gpu.py): which body ssg_conv2d_wgrad_f32 would
+// run for this descriptor under kernel id 50 / 51 -- 1 = wgrad_dma_x3_kernel, 2 = the split-once body of conv_wgrad_dma_k32.hip;
+// 0 = the descriptor does not validate or maps to another kernel id.
+extern "C" int ssg_wgrad_dma_body(const ssg_wgrad_desc* d) {
+  if (!d || validate(d) != SSG_OK) return 0;
+  const Plan p = make_plan(d);
+  if (p.kind != WG_MFMA || !wgrad_uses_dma(p.variant) || !(d->flags & 1)) return 0;
+  return ssg_wgrad_dma_split_body(wgrad_args(d, p), p.variant, (long long)p.mt * p.nt * p.splits);
 }

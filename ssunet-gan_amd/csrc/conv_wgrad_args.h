@@ -16,6 +16,13 @@ struct WgArgs {
 
 // conv_wgrad_dma.hip: LDS-DMA pipeline for Cout > 32 (variant 0 = <128,128>, 1 = <128,64>)
 int ssg_wgrad_dma_launch(const WgArgs& a, int variant, dim3 grid, hipStream_t st, bool split);
+// which body a split launch runs: 1 = wgrad_dma_x3_kernel (operands split as they leave LDS), 2 = the split-once body below
+int ssg_wgrad_dma_split_body(const WgArgs& a, int variant, long long workgroups);
+
+// conv_wgrad_dma_k32.hip: the split (bf16x3) form of the above with operands split once on the way into LDS, 32-pixel K-steps on
+// v_mfma_f32_16x16x32_bf16; same grid, K-slices and slabs.  Chosen inside ssg_wgrad_dma_launch where ssg_wgrad_dma_k32_ok holds.
+bool ssg_wgrad_dma_k32_ok(const WgArgs& a);
+int ssg_wgrad_dma_k32_launch(const WgArgs& a, int variant, dim3 grid, hipStream_t st);
 
 // conv_wgrad_halo.hip: 3x3 stride-1 weight gradient with an LDS-resident pixel window
 // (variant 0 = 9 taps x 32 channels x 128 output channels per workgroup, 1 = 9 x 64 x 64)

@@ -222,9 +222,21 @@ __global__ __launch_bounds__(256) void wgrad_dma_x3_kernel(const WgArgs a) { wgr
 
 }  // namespace
 
+// Which body a split launch runs: the split-once body (2) wherever its preconditions hold, except one measured class that stays on
+// wgrad_dma_x3_kernel (1) -- minimum-length K-slices (<= 16 steps = 256 pixels: 8 steps of the new body, so prologue, slab store
+// and reduce weigh as much as the MFMAs) with a partly filled last row block (M % 128 != 0) on a grid of more than two workgroups
+// per CU (256 CUs; this body fits three per CU, the split-once body two).  DESIGN.md 3.17: 48 -> 1536 3x3 at 16^2 (M = 432, 768
+// workgroups) 72.9 us here, 73.9 us there; the full-row-block shapes of the same grid and slice length gain 8-9 % there.
+int ssg_wgrad_dma_split_body(const WgArgs& a, int variant, long long workgroups) {
+  if (!ssg_wgrad_dma_k32_ok(a)) return 1;
+  if (a.steps_per_split <= 16 && a.M % 128 != 0 && workgroups > 2 * 256) return 1;
+  return 2;
+}
+
 int ssg_wgrad_dma_launch(const WgArgs& a0, int variant, dim3 grid, hipStream_t st, bool split) {
   WgArgs a = a0;
   a.xcd_swizzle = ssg_xcd_swizzle();
+  if (split && ssg_wgrad_dma_split_body(a, variant, (long long)grid.x * grid.y * grid.z) == 2) return ssg_wgrad_dma_k32_launch(a, variant, grid, st);
   if (split) {
     if (variant == 0) hipLaunchKernelGGL((wgrad_dma_x3_kernel<128, 128>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((wgrad_dma_x3_kernel<128, 64>), grid, dim3(256), 0, st, a);
