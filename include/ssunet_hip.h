@@ -142,6 +142,29 @@ int ssg_conv2d_bf16x1_f32(const ssg_conv_desc* d, const void* w_bf16x1, void* st
 int64_t ssg_pack_weights_bf16x1_bytes(int R, int Kp, int BN);
 int ssg_pack_weights_bf16x1(const float* w_packed, int R, int Kp, int BN, void* out, void* stream);
 
+/* Opt-in bf16x1 kernels for the 3x3 STRIDE-2 pad-1 conv (models_seg_gan.py:37-39, the discriminator's s2 blocks) and its input
+ * gradient (conv_s2_k32_x1.hip; ops.conv2d(..., precision='bf16x1')): the contract of ssg_conv2d_bf16x1_f32 -- operands rounded once
+ * to bf16, fp32 accumulation, fp32 tensors, non-finite results those of the fp32 kernels -- with one input (C2 = 0) and no res.
+ * ssg_conv2d_bf16x1_s2_*: the forward.  Legal: the nine row-major taps (dy = t / 3 - 1, dx = t % 3 - 1), kmode 0, in_sy = in_sx = 2,
+ * out_s* = 1, out_o* = 0, C1 % 32 == 0, Cout % 64 == 0, Kp = 9 C1, GW >= 17, any H / W, 16-byte alignment, ld % 4 == 0, input below
+ * 4 GiB, act none / ReLU / leaky ReLU, optional bias; bnpart, ws, parity_merge, in_scale, bwd_x, res unset.  The pack is
+ * ssg_pack_weights_bf16x1's.  Kernel ids 73 / 74 = conv_s2_k32_x1_kernel<128,9> / <64,9> (4 x 32-pixel tiles).
+ * ssg_conv2d_bf16x1_cls_*: ONE parity class of the input gradient, a launch of the per-class form of `parity_merge` above: ntaps =
+ * 1 / 2 / 4 distinct taps with dy, dx in {0, +1}, in_s* = 1, out_sy = out_sx = 2, out_oy / out_ox in {0, 1}, in1 = dy (C1 % 32 == 0),
+ * Cout = gradient rows (% 64 == 0), Kp = ntaps * C1, GW >= 17, (GH - 1) * 2 + out_oy < OH (and the same in x).  The pack is
+ * ssg_pack_weights_bf16x1_taps(d->w rows [R][Kp] in kmode 0 with `ntaps` taps, R, Kp, ntaps, BN = the code _cls_ok returned):
+ * layout [R/bn][Kp/32 steps = chunk32 * ntaps + tap][bn/16 fragments][64 lanes][16 B] (Kp % (32 ntaps) == 0).  Kernel ids 75 / 76,
+ * 77 / 78, 79 / 80 = conv_s2_k32_x1_kernel<128 / 64> with 1, 2, 4 taps (8 x 32-pixel tiles).
+ * Both launchers validate on the host and return a status before any launch; _ok returns 0 or the pack format code (1128 / 1064). */
+int ssg_conv2d_bf16x1_s2_ok(const ssg_conv_desc* d);
+int ssg_conv2d_bf16x1_s2_kernel_id(const ssg_conv_desc* d);
+int ssg_conv2d_bf16x1_s2_f32(const ssg_conv_desc* d, const void* w_bf16x1, void* stream);
+int ssg_conv2d_bf16x1_cls_ok(const ssg_conv_desc* d);
+int ssg_conv2d_bf16x1_cls_kernel_id(const ssg_conv_desc* d);
+int ssg_conv2d_bf16x1_cls_f32(const ssg_conv_desc* d, const void* w_bf16x1, void* stream);
+int64_t ssg_pack_weights_bf16x1_taps_bytes(int R, int Kp, int ntaps, int BN);
+int ssg_pack_weights_bf16x1_taps(const float* w_packed, int R, int Kp, int ntaps, int BN, void* out, void* stream);
+
 /* Launches whose pixel-tile count leaves most of the chip idle (the 16x16 / 32x32 levels of archs.py:583-589, the
  * Cout <= 64 input gradients of SPADE's gamma|beta conv normalization.py:94-96, batch-1 inference api.py:322) split the
  * reduction over 16-channel chunks into slabs; an ordered second stage adds the slabs and applies bias / res / act

@@ -447,15 +447,27 @@ def _x1_routed(precision, stride, pad, wscale, fused):
     return stride == 1 and _pad4(pad) == (1, 1, 1, 1) and wscale is None
 
 
-def _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=None, out=None, wscale=None, want_bn=False, in_affine=None, precision='fp32'):
+def _x1_s2_routed(precision, x1_s2, stride, pad, wscale):
+    """True where a call from the single-conv node (`x1_s2`: _Conv2d passes it, the block nodes never do) under 'bf16x1' asks the
+    stride-2 bf16x1 kernels first: a stride-2 pad-1 conv of unscaled weights."""
+    return bool(x1_s2) and precision == 'bf16x1' and stride == 2 and _pad4(pad) == (1, 1, 1, 1) and wscale is None
+
+
+def _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=None, out=None, wscale=None, want_bn=False, in_affine=None, precision='fp32',
+                   x1_s2=False):
     """Returns y, or (y, part) with want_bn: part = per-tile batch-norm partial sums of y from the conv epilogue, or None when
     the kernel this shape maps to has none (the batch norm then runs its own statistics pass).  in_affine: see _conv_launch; the
     result is None (nothing launched) when the library declines.  precision='bf16x1': a unit-stride 3x3 pad-1 conv runs on
     _conv_bf16x1_impl where conv2d_bf16x1_ok holds (part is then None: that launcher has no statistics epilogue) and on the
-    fp32-class kernel below where it refuses."""
+    fp32-class kernel below where it refuses.  x1_s2 (the single-conv node only): a 3x3 stride-2 pad-1 conv without x2 / res asks
+    _conv_s2_bf16x1_impl first in the same way."""
     if _x1_routed(precision, stride, pad, wscale, in_affine) and conv2d_bf16x1_ok(x1, weight, x2=x2, res=res):
         y = _conv_bf16x1_impl(x1, weight, bias, act, slope, x2=x2, res=res, out=out)
         return (y, None) if want_bn else y
+    if _x1_s2_routed(precision, x1_s2, stride, pad, wscale) and x2 is None and res is None and in_affine is None:
+        y = _conv_s2_bf16x1_impl(x1, weight, bias, act, slope, out=out)
+        if y is not None:
+            return (y, None) if want_bn else y
     o, i, kh, kw = weight.shape
     n, c1, h, w = x1.shape
     c2 = x2.shape[1] if x2 is not None else 0
@@ -478,15 +490,20 @@ def _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=None, out=
     return (out, part) if want_bn else out
 
 
-def _conv_dgrad_impl(dy, weight, stride, pad, h, w, c_lo, c_hi, res=None, wscale=None, bwd_stats=None, precision='fp32'):
+def _conv_dgrad_impl(dy, weight, stride, pad, h, w, c_lo, c_hi, res=None, wscale=None, bwd_stats=None, precision='fp32', x1_s2=False):
     """Input gradient for input channels [c_lo, c_hi) -> NHWC tensor [N, c_hi-c_lo, h, w].
     `res` (same shape) is added in the epilogue: gradient accumulation without an extra pass.
     bwd_stats = (x, stats, act, slope): the gradient is that of act(bn(x)); returns (g, part) -- the MASKED gradient and the per-tile rows
     (sum g, sum g * (x - mean)) of the batch-norm backward from the epilogue (ssg_conv_desc.bwd_x) -- or None, with nothing launched,
     where the kernel this launch maps to has no such epilogue.  precision='bf16x1': a unit-stride 3x3 pad-1 gradient is
-    _conv_dgrad_bf16x1_impl's where that takes it, and the fp32-class kernel's below where it refuses."""
+    _conv_dgrad_bf16x1_impl's where that takes it, and the fp32-class kernel's below where it refuses.  x1_s2 (the single-conv node
+    only): a 3x3 stride-2 pad-1 gradient without res is _conv_dgrad_s2_bf16x1_impl's where all four parity classes are legal."""
     if _x1_routed(precision, stride, pad, wscale, bwd_stats):
         dx = _conv_dgrad_bf16x1_impl(dy, weight, h, w, c_lo, c_hi, res=res)
+        if dx is not None:
+            return dx
+    if _x1_s2_routed(precision, x1_s2, stride, pad, wscale) and res is None and bwd_stats is None:
+        dx = _conv_dgrad_s2_bf16x1_impl(dy, weight, h, w, c_lo, c_hi)
         if dx is not None:
             return dx
     o, i, kh, kw = weight.shape
@@ -587,7 +604,8 @@ def _act_bwd(y, dy, act, slope):
 
 class _Conv2d(torch.autograd.Function):
     """F.conv2d (+bias, +activation, optional second input = channel concat) on MFMA.  `precision` (see _conv_fwd_impl) is the
-    forward's and, kept on ctx, that of the three gradients."""
+    forward's and, kept on ctx, that of the three gradients.  This node, and no other, also asks the stride-2 bf16x1 kernels
+    (x1_s2) under 'bf16x1'."""
 
     @staticmethod
     def forward(ctx, x1, x2, weight, bias, stride, pad, act, slope, res=None, want_bn=False, precision='fp32'):
@@ -595,7 +613,7 @@ class _Conv2d(torch.autograd.Function):
         x1 = to_nhwc(x1)
         x2 = to_nhwc(x2) if x2 is not None else None
         res = to_nhwc(res) if res is not None else None
-        r = _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=res, want_bn=want_bn, precision=precision)
+        r = _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=res, want_bn=want_bn, precision=precision, x1_s2=True)
         y, part = r if want_bn else (r, None)
         ctx.cfg = (stride, pad, act, slope, precision)
         ctx.save_for_backward(x1, x2, weight, y if act != ACT_NONE else None)
@@ -619,9 +637,9 @@ class _Conv2d(torch.autograd.Function):
         n, c1, h, w = x1.shape
         dx1 = dx2 = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx1 = _conv_dgrad_impl(dy, weight, stride, pad, h, w, 0, c1, precision=precision)
+            dx1 = _conv_dgrad_impl(dy, weight, stride, pad, h, w, 0, c1, precision=precision, x1_s2=True)
         if x2 is not None and ctx.needs_input_grad[1]:
-            dx2 = _conv_dgrad_impl(dy, weight, stride, pad, h, w, c1, c1 + x2.shape[1], precision=precision)
+            dx2 = _conv_dgrad_impl(dy, weight, stride, pad, h, w, c1, c1 + x2.shape[1], precision=precision, x1_s2=True)
         if ctx.needs_input_grad[2]:
             dw = _conv_wgrad_impl(x1, x2, dy, weight.shape, stride, pad, precision=precision)
         if ctx.has_bias and ctx.needs_input_grad[3]:
@@ -630,15 +648,20 @@ class _Conv2d(torch.autograd.Function):
         return dx1, dx2, dw, db, None, None, None, None, dres, None, None
 
 
-def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, x2=None, res=None, bn_stats=False):
+def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, x2=None, res=None, bn_stats=False, precision='fp32'):
     """F.conv2d on the HIP kernels.  `padding`: int or (top, bottom, left, right) (TF-"same" static
     padding of the EfficientNet convs is asymmetric); `x2`: second tensor concatenated after x;
     `res`: tensor added in the epilogue before the activation (act(conv(x) + bias + res)).
     `bn_stats=True`: returns (y, part) -- `part` are the per-tile (sum, sum of squares) of y from the conv epilogue (empty when
-    this shape's kernel has none); hand it to batch_norm_act(y, bn, stats_part=part) to skip its statistics pass."""
+    this shape's kernel has none); hand it to batch_norm_act(y, bn, stats_part=part) to skip its statistics pass.
+    `precision='bf16x1'` (opt-in, an approximation: both operands rounded once to bf16, fp32 accumulation): a 3x3 pad-1 conv of
+    stride 1 or 2 asks the one-term kernels first, in the forward and in each of its gradients, and runs today's kernel wherever
+    their predicates refuse -- it never raises for a shape; `part` of a routed forward is empty.  'fp32' (default): today's launches."""
     _lib.require_gpu(x)
+    if precision not in _PRECISIONS:
+        raise ValueError('conv2d: unknown precision %r (one of %s)' % (precision, ', '.join(_PRECISIONS)))
     pad = tuple(int(v) for v in padding) if isinstance(padding, (tuple, list)) else int(padding)
-    y, part = _Conv2d.apply(x, x2, weight, bias, int(stride), pad, int(act), float(slope), res, bool(bn_stats), 'fp32')
+    y, part = _Conv2d.apply(x, x2, weight, bias, int(stride), pad, int(act), float(slope), res, bool(bn_stats), precision)
     return (y, part) if bn_stats else y
 
 
@@ -784,7 +807,8 @@ class train_precision(_precision):
     """with ops.train_precision('bf16x1'): ...   -- autograd nodes that have a bf16x1 route (blocks._BasicBlockFn,
     blocks._FrozenBasicBlockFn) run their 3x3 stride-1 convs, forward, input gradient and weight gradient, with both operands
     rounded once to bf16 (fp32 accumulation, fp32 tensors: an approximation) wherever the kernels' predicates hold, and stay on the
-    fp32-class kernels elsewhere.  'fp32' (the default) launches exactly what runs without the context.  A node reads the mode in
+    fp32-class kernels elsewhere.  models_seg_gan.ConvolutionalBlock (the discriminator) hands the mode to conv2d(precision=), whose
+    node also has the stride-2 routes.  'fp32' (the default) launches exactly what runs without the context.  A node reads the mode in
     its forward and keeps it: its backward uses the forward's mode whatever is set when .backward() runs."""
     _state = ['fp32']
 
@@ -840,14 +864,130 @@ def _conv_dgrad_bf16x1_impl(dy, weight, h, w, c_lo, c_hi, res=None):
     return dx
 
 
-def conv2d_bf16x1_train(x, weight, bias=None, act=ACT_NONE, slope=0.0, x2=None, res=None):
+# ----------------------------------------------------------------------------- opt-in bf16x1: the stride-2 conv of the single-conv node
+# csrc/conv_s2_k32_x1.hip: the 3x3 stride-2 pad-1 forward (ssg_conv2d_bf16x1_s2_f32) and its input gradient as four parity-class
+# launches (ssg_conv2d_bf16x1_cls_f32; the tap lists are those of the per-class launches of _conv_dgrad_impl).  Reached only from
+# _Conv2d under precision='bf16x1'; the stride-2 weight gradient stays on the fp32-class kernel.  Labels in tables of their own.
+_X1_S2_LABELS = {73: 'conv_s2_k32_x1_kernel<128,9>', 74: 'conv_s2_k32_x1_kernel<64,9>'}
+_X1_CLS_LABELS = {75: 'conv_s2_k32_x1_kernel<128,1>', 76: 'conv_s2_k32_x1_kernel<64,1>', 77: 'conv_s2_k32_x1_kernel<128,2>',
+                  78: 'conv_s2_k32_x1_kernel<64,2>', 79: 'conv_s2_k32_x1_kernel<128,4>', 80: 'conv_s2_k32_x1_kernel<64,4>'}
+_X1_S2_KIND = (_X1_S2_LABELS, 'ssg_conv2d_bf16x1_s2_kernel_id', _CONV_SHAPE)
+_X1_CLS_KIND = (_X1_CLS_LABELS, 'ssg_conv2d_bf16x1_cls_kernel_id', _CONV_SHAPE)
+
+
+def _s2_classes():
+    """(py, px, taps) of the four output-parity classes of a 3x3 stride-2 pad-1 input gradient: _conv_dgrad_impl's lists."""
+    return [(py, px, [(ky, kx, (py + 1 - ky) // 2, (px + 1 - kx) // 2) for ky in range(3) for kx in range(3)
+                      if (py + 1 - ky) % 2 == 0 and (px + 1 - kx) % 2 == 0]) for py in range(2) for px in range(2)]
+
+
+def _x1_s2_desc(x, weight, out=None):
+    """ssg_conv_desc of the stride-2 bf16x1 forward for these tensors (stand-in pointers as in _x1_desc)."""
+    ld = nhwc_ld(x)
+    n, c1, h, w = x.shape
+    o = weight.shape[0]
+    oh, ow = _out_hw(h, w, 3, 3, 2, 1)
+    return _conv_desc((x.data_ptr(), ld) if ld is not None else (16, pad4(c1)), c1, None, 0, (n, h, w), 16, 9 * c1, 0, None, None,
+                      _at(out) if out is not None else (16, pad4(o)), o, (oh, ow, oh, ow), 2, 1, (0, 0), _X1_TAPS, ACT_NONE, 0.0)
+
+
+def conv2d_bf16x1_s2_ok(x, weight):
+    """True where the stride-2 bf16x1 forward takes these tensors (ssg_conv2d_bf16x1_s2_ok): a 3x3 weight, Cin % 32 == 0,
+    Cout % 64 == 0, an output at least 17 pixels wide, fp32 tensors below 4 GiB.  Launches nothing."""
+    if not _x1_shapes_ok(x, weight, None, None) or min(x.shape[2:]) < 1:
+        return False
+    return call('ssg_conv2d_bf16x1_s2_ok', C.byref(_x1_s2_desc(x, weight))) != 0
+
+
+def _conv_s2_bf16x1_impl(x, weight, bias, act, slope, out=None):
+    """act(conv3x3(x, weight, stride 2, padding 1) + bias) with x and the weight rounded once to bf16.  Returns None, with nothing
+    launched, where ssg_conv2d_bf16x1_s2_ok refuses (the caller then takes the fp32-class kernel)."""
+    if not _x1_shapes_ok(x, weight, None, None):
+        return None
+    x = to_nhwc(x.detach())
+    n, c1, h, w = x.shape
+    o = weight.shape[0]
+    d = _x1_s2_desc(x, weight, out)
+    if not call('ssg_conv2d_bf16x1_s2_ok', C.byref(d)):
+        return None
+    wpk, kp, kmode = _pack(weight, 0, _X1_TAPS, c1, c1)
+    oh, ow = _out_hw(h, w, 3, 3, 2, 1)
+    if out is None:
+        out = new_nhwc(n, o, oh, ow, x.device)
+    d.out, d.ldo = _at(out)
+    d.w = wpk.data_ptr(); d.Kp = kp; d.kmode = kmode
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.act = int(act); d.slope = float(slope)
+    fmt = call('ssg_conv2d_bf16x1_s2_ok', C.byref(d))
+    if not fmt:
+        return None
+    pack = _x1_pack(weight, wpk, kp, fmt)
+    _timed_call(_X1_S2_KIND, 'ssg_conv2d_bf16x1_s2_f32', d, (ptr(pack),), (n, oh, ow, c1, o, 9, 2, 1), 2.0 * n * oh * ow * o * c1 * 9, tag=_ROLE[0])
+    return out
+
+
+def _x1_cls_pack(weight, wpk, kp, taps, fmt, row0, rows):
+    """The bf16 pack of rows [row0, row0 + rows) of the transposed kmode-0 matrix `wpk` for one parity class's taps
+    (ssg_pack_weights_bf16x1_taps), cached beside the other bf16x1 packs of the weight."""
+    cache = _stamped_cache(weight, '_ssg_pack_bf16x1')
+    key = ('cls', tuple(taps), row0, rows, fmt)
+    hit = cache.get(key)
+    if hit is None:
+        nbytes = call('ssg_pack_weights_bf16x1_taps_bytes', rows, kp, len(taps), fmt)
+        hit = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
+        call('ssg_pack_weights_bf16x1_taps', wpk.data_ptr() + row0 * kp * 4, rows, kp, len(taps), fmt, ptr(hit), stream_ptr())
+        cache[key] = hit
+    return hit
+
+
+def _conv_dgrad_s2_bf16x1_impl(dy, weight, h, w, c_lo, c_hi, out=None):
+    """Input gradient [N, c_hi - c_lo, h, w] of the 3x3 stride-2 pad-1 conv with dy and the weight rounded once to bf16: four
+    launches of ssg_conv2d_bf16x1_cls_f32, one per output-parity class, each written at stride 2 and offset (py, px).  Returns None,
+    with nothing launched or allocated, unless ssg_conv2d_bf16x1_cls_ok takes all four classes."""
+    o, i, kh, kw = weight.shape
+    n, _, oh, ow = dy.shape
+    rows = c_hi - c_lo
+    if (kh, kw) != (3, 3) or (oh, ow) != _out_hw(h, w, 3, 3, 2, 1) or o % 16 or rows <= 0 or dy.dtype != torch.float32 or weight.dtype != torch.float32:
+        return None
+    dy = to_nhwc(dy.detach())
+    descs = []
+    for py, px, taps in _s2_classes():
+        gh, gw = (h - py + 1) // 2, (w - px + 1) // 2
+        d = _conv_desc(_at(dy), o, None, 0, (n, oh, ow), 16, len(taps) * o, 0, None, None, _at(out) if out is not None else (16, pad4(rows)), rows,
+                       (gh, gw, h, w), 1, 2, (py, px), taps, ACT_NONE, 0.0)
+        if not call('ssg_conv2d_bf16x1_cls_ok', C.byref(d)):
+            return None
+        descs.append((d, taps, gh, gw))
+    dx = out if out is not None else new_nhwc(n, rows, h, w, dy.device)
+    for d, taps, gh, gw in descs:
+        wpk, kp, kmode = _pack(weight, 1, taps, o, o)
+        d.w = wpk.data_ptr() + c_lo * kp * 4; d.Kp = kp; d.kmode = kmode
+        d.out, d.ldo = _at(dx)
+        fmt = call('ssg_conv2d_bf16x1_cls_ok', C.byref(d))
+        if not fmt:
+            raise RuntimeError('conv bf16x1 cls: the predicate changed its answer between the check and the launch')
+        pack = _x1_cls_pack(weight, wpk, kp, taps, fmt, c_lo, rows)
+        _timed_call(_X1_CLS_KIND, 'ssg_conv2d_bf16x1_cls_f32', d, (ptr(pack),), (n, gh, gw, o, rows, len(taps), 1, 2), 2.0 * n * gh * gw * o * rows * len(taps))
+    return dx
+
+
+def conv2d_bf16x1_train(x, weight, bias=None, act=ACT_NONE, slope=0.0, x2=None, res=None, stride=1):
     """The differentiable form of `conv2d_bf16x1`: forward on conv_halo_k32_x1_kernel, gradients for x, x2 and res on the same
     kernel (dy and the transposed weight rounded to bf16), weight gradient on wgrad_k32_x1_kernel (x and dy rounded), bias gradient
     by the fp32 channel sum.  A gradient whose own predicate refuses (a 32-channel slice, say) runs on the fp32-class kernel.
-    Raises ValueError where `conv2d_bf16x1_ok` is false; there is no CPU fallback."""
+    stride=2 (no x2 / res): forward and input gradient on conv_s2_k32_x1_kernel where `conv2d_bf16x1_s2_ok` holds, the weight
+    gradient on the fp32-class kernel.  Raises ValueError where `conv2d_bf16x1_ok` / `conv2d_bf16x1_s2_ok` is false; there is no
+    CPU fallback."""
     for t in (x, weight, bias, x2, res):
         if t is not None:
             _lib.require_gpu(t)
+    if stride == 2:
+        if x2 is not None or res is not None or not conv2d_bf16x1_s2_ok(x, weight):
+            raise ValueError('conv2d_bf16x1_train: no stride-2 bf16x1 kernel for x %s weight %s%s (conv2d_bf16x1_s2_ok is False)' % (
+                tuple(x.shape), tuple(weight.shape), ' with x2 / res' if (x2 is not None or res is not None) else ''))
+        return _Conv2d.apply(x, None, weight, bias, 2, 1, int(act), float(slope), None, False, 'bf16x1')[0]
+    if stride != 1:
+        raise ValueError('conv2d_bf16x1_train: stride %r (1 or 2)' % (stride,))
     if not conv2d_bf16x1_ok(x, weight, x2=x2, res=res):
         raise ValueError('conv2d_bf16x1_train: no bf16x1 kernel for x %s x2 %s weight %s res %s (conv2d_bf16x1_ok is False)' % (
             tuple(x.shape), None if x2 is None else tuple(x2.shape), tuple(weight.shape), None if res is None else tuple(res.shape)))
