@@ -262,6 +262,23 @@ int64_t ssg_conv2d_wgrad_bf16x1_workspace_bytes(const ssg_wgrad_desc* d);
 int ssg_conv2d_wgrad_bf16x1_f32(const ssg_wgrad_desc* d, void* stream);
 int ssg_conv2d_wgrad_bf16x1_kernel_id(const ssg_wgrad_desc* d);
 
+/* Opt-in bf16x1 weight gradient of the 3x3 STRIDE-2 pad-1 conv (conv_wgrad_s2_k32_x1.hip; precision 'bf16x1' with wgrad_s2 'bf16x1'):
+ * the contract, rounding, error bound and non-finite guard of the group above, dw[ky][kx][ci][co] = sum in[n, 2oy + ky - 1,
+ * 2ox + kx - 1, ci] * dout[n, oy, ox, co].  A route of its own: neither ssg_conv2d_wgrad_f32 nor ssg_conv2d_wgrad_bf16x1_f32 comes here.
+ * ssg_conv2d_wgrad_bf16x1_s2_ok: 1 where the launch takes `d` -- the nine row-major taps (dy = t / 3 - 1, dx = t % 3 - 1, ky = t / 3,
+ *   kx = t % 3), in_sy == in_sx == 2, GH == (H + 1) / 2, GW == (W + 1) / 2, GW >= 17, C1 % 64 == 0, C2 == 0 (no concat),
+ *   Cout % 64 == 0, Cin_real == C1, pixel strides multiples of 4, tensors within 32-bit byte offsets, in_scale == NULL -- else 0.
+ *   Pointers are not read.
+ * ssg_conv2d_wgrad_bf16x1_s2_workspace_bytes: bytes of d->ws for the split-K slabs (0 where refused).
+ * ssg_conv2d_wgrad_bf16x1_s2_f32 validates on the host and returns a status ("wgrad bf16x1 s2: ..." in ssg_last_error) before any
+ *   launch; d->flags is ignored.
+ * ssg_conv2d_wgrad_bf16x1_s2_kernel_id: 81 / 82 = wgrad_s2_k32_x1_kernel<4> / <2> (128 / 64 output channels per workgroup, by
+ *   Cout % 128), SSG_EINVAL where refused. */
+int ssg_conv2d_wgrad_bf16x1_s2_ok(const ssg_wgrad_desc* d);
+int64_t ssg_conv2d_wgrad_bf16x1_s2_workspace_bytes(const ssg_wgrad_desc* d);
+int ssg_conv2d_wgrad_bf16x1_s2_f32(const ssg_wgrad_desc* d, void* stream);
+int ssg_conv2d_wgrad_bf16x1_s2_kernel_id(const ssg_wgrad_desc* d);
+
 /* Attention gate of AttUNet (archs.py:115-144, `x * psi`): y[p][c] = x[p][c] * sigmoid(g[p]) with one gate
  * logit per pixel (g is the 1-channel BatchNorm output, pixel stride ldg); the sigmoid is folded in.
  * backward: dx = dy * s, dg[p] = (sum_c dy*x) * s * (1 - s) (written as a 4-float pixel: value, 0, 0, 0). */

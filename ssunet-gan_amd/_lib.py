@@ -107,6 +107,10 @@ SIGNATURES = {
     'ssg_conv2d_wgrad_bf16x1_kernel_id': [C.POINTER(WgradDesc)],
     'ssg_conv2d_wgrad_bf16x1_workspace_bytes': [C.POINTER(WgradDesc)],
     'ssg_conv2d_wgrad_bf16x1_f32': [C.POINTER(WgradDesc), _P],
+    'ssg_conv2d_wgrad_bf16x1_s2_ok': [C.POINTER(WgradDesc)],
+    'ssg_conv2d_wgrad_bf16x1_s2_kernel_id': [C.POINTER(WgradDesc)],
+    'ssg_conv2d_wgrad_bf16x1_s2_workspace_bytes': [C.POINTER(WgradDesc)],
+    'ssg_conv2d_wgrad_bf16x1_s2_f32': [C.POINTER(WgradDesc), _P],
     'ssg_bn_stats_from_partials_workspace_bytes': [_I, _I],
     'ssg_bn_stats_from_partials_f32': [_P, _I, _I, _P, _D, _P, _P],
     'ssg_conv2d_wgrad_kernel_id': [C.POINTER(WgradDesc)],
@@ -205,6 +209,7 @@ SIGNATURES['ssg_convert_bf16_to_f32'] = [_P, _I, _L, _I, _P, _I, _P]
 _RESTYPES = {
     'ssg_conv2d_wgrad_workspace_bytes': C.c_int64,
     'ssg_conv2d_wgrad_bf16x1_workspace_bytes': C.c_int64,
+    'ssg_conv2d_wgrad_bf16x1_s2_workspace_bytes': C.c_int64,
     'ssg_conv2d_workspace_bytes': C.c_int64,
     'ssg_pack_weights_split_bytes': C.c_int64,
     'ssg_pack_weights_bf16x1_bytes': C.c_int64,
@@ -220,7 +225,7 @@ _RESTYPES = {
     'ssg_conv2d_thin_bf16_wgrad_workspace_bytes': C.c_int64,
     'ssg_bn_stats_from_partials_workspace_bytes': C.c_int64,
 }
-_NO_STATUS = set(_RESTYPES) | {'ssg_abi_version', 'ssg_conv2d_split_bn', 'ssg_conv2d_in_affine_ok', 'ssg_conv2d_wgrad_in_affine_ok', 'ssg_conv2d_bwd_stats_ok', 'ssg_conv2d_kernel_id', 'ssg_conv2d_bnpart_rows', 'ssg_conv2d_bf16x1_ok', 'ssg_conv2d_bf16x1_kernel_id', 'ssg_conv2d_bf16x1_s2_ok', 'ssg_conv2d_bf16x1_s2_kernel_id', 'ssg_conv2d_bf16x1_cls_ok', 'ssg_conv2d_bf16x1_cls_kernel_id', 'ssg_conv2d_wgrad_bf16x1_ok', 'ssg_conv2d_wgrad_bf16x1_kernel_id', 'ssg_conv2d_wgrad_kernel_id', 'ssg_dwconv2d_kernel_id',
+_NO_STATUS = set(_RESTYPES) | {'ssg_abi_version', 'ssg_conv2d_split_bn', 'ssg_conv2d_in_affine_ok', 'ssg_conv2d_wgrad_in_affine_ok', 'ssg_conv2d_bwd_stats_ok', 'ssg_conv2d_kernel_id', 'ssg_conv2d_bnpart_rows', 'ssg_conv2d_bf16x1_ok', 'ssg_conv2d_bf16x1_kernel_id', 'ssg_conv2d_bf16x1_s2_ok', 'ssg_conv2d_bf16x1_s2_kernel_id', 'ssg_conv2d_bf16x1_cls_ok', 'ssg_conv2d_bf16x1_cls_kernel_id', 'ssg_conv2d_wgrad_bf16x1_ok', 'ssg_conv2d_wgrad_bf16x1_kernel_id', 'ssg_conv2d_wgrad_bf16x1_s2_ok', 'ssg_conv2d_wgrad_bf16x1_s2_kernel_id', 'ssg_conv2d_wgrad_kernel_id', 'ssg_dwconv2d_kernel_id',
                                 'ssg_spade_conv_modulate_ok', 'ssg_se_gate_ok'}
 
 ABI_VERSION = 10         # ssg_abi_version() of the library this ctypes table (ConvDesc layout, SIGNATURES) was written against

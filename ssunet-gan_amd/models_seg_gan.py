@@ -60,11 +60,11 @@ class ConvolutionalBlock(nn.Module):
                                      act=a, slope=sl, n_power_iterations=sn.n_power_iterations if conv.training else 0, eps=sn.eps)
         else:
             # ops.train_precision: read here, in the forward; the conv node keeps it for its backward.  The spectral-norm path stays fp32-class.
-            precision = ops.train_precision_mode()
+            precision, wgrad_s2 = ops.train_precision_mode(), ops.train_wgrad_s2_mode()
 
             def run(a, sl, bn_stats=False):
                 return ops.conv2d(input, conv.weight, conv.bias, conv.stride[0], conv.padding[0], act=a, slope=sl, bn_stats=bn_stats,
-                                  precision=precision)
+                                  precision=precision, wgrad_s2=wgrad_s2)
         if not self._bn:
             return run(act, slope)
         bn = self.conv_block[1]

@@ -559,12 +559,27 @@ def _conv_dgrad_impl(dy, weight, stride, pad, h, w, c_lo, c_hi, res=None, wscale
     return dx
 
 
-def _conv_wgrad_impl(x1, x2, dy, weight_shape, stride, pad, in_affine=None, precision='fp32'):
+def _check_wgrad_s2(who, precision, wgrad_s2):
+    """The second switch's values: 'fp32' | 'bf16x1', the latter only beside precision='bf16x1'."""
+    if wgrad_s2 not in _PRECISIONS:
+        raise ValueError('%s: unknown wgrad_s2 %r (one of %s)' % (who, wgrad_s2, ', '.join(_PRECISIONS)))
+    if wgrad_s2 == 'bf16x1' and precision != 'bf16x1':
+        raise ValueError("%s: wgrad_s2='bf16x1' needs precision='bf16x1' (got %r)" % (who, precision))
+
+
+def _conv_wgrad_impl(x1, x2, dy, weight_shape, stride, pad, in_affine=None, precision='fp32', wgrad_s2='fp32'):
     """in_affine = (scale, shift, act, slope): the x operand is act(x1 * scale + shift) (ssg_wgrad_desc.in_scale); returns None,
     with nothing launched, when the kernel this shape maps to has no such transform.  precision='bf16x1': a unit-stride 3x3 pad-1
-    weight gradient is _conv_wgrad_bf16x1_impl's where that takes it, and the fp32-class kernel's below where it refuses."""
+    weight gradient is _conv_wgrad_bf16x1_impl's where that takes it, and the fp32-class kernel's below where it refuses.
+    wgrad_s2='bf16x1' (beside precision='bf16x1' only; the single-conv node passes it, the block nodes never do): a 3x3 stride-2
+    pad-1 weight gradient without x2 / in_affine is _conv_wgrad_s2_bf16x1_impl's where that takes it."""
     if _x1_routed(precision, stride, pad, None, in_affine):
         dw = _conv_wgrad_bf16x1_impl(x1, x2, dy, weight_shape)
+        if dw is not None:
+            return dw
+    if (precision == 'bf16x1' and wgrad_s2 == 'bf16x1' and stride == 2 and _pad4(pad) == (1, 1, 1, 1) and x2 is None
+            and in_affine is None):
+        dw = _conv_wgrad_s2_bf16x1_impl(x1, dy, weight_shape)
         if dw is not None:
             return dw
     o, i, kh, kw = weight_shape
@@ -605,17 +620,17 @@ def _act_bwd(y, dy, act, slope):
 class _Conv2d(torch.autograd.Function):
     """F.conv2d (+bias, +activation, optional second input = channel concat) on MFMA.  `precision` (see _conv_fwd_impl) is the
     forward's and, kept on ctx, that of the three gradients.  This node, and no other, also asks the stride-2 bf16x1 kernels
-    (x1_s2) under 'bf16x1'."""
+    (x1_s2) under 'bf16x1', and the stride-2 bf16x1 weight gradient where `wgrad_s2` (kept on ctx beside it) says so."""
 
     @staticmethod
-    def forward(ctx, x1, x2, weight, bias, stride, pad, act, slope, res=None, want_bn=False, precision='fp32'):
+    def forward(ctx, x1, x2, weight, bias, stride, pad, act, slope, res=None, want_bn=False, precision='fp32', wgrad_s2='fp32'):
         ctx.set_materialize_grads(False)       # no zero tensor for the (non-differentiable) statistics output's gradient
         x1 = to_nhwc(x1)
         x2 = to_nhwc(x2) if x2 is not None else None
         res = to_nhwc(res) if res is not None else None
         r = _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=res, want_bn=want_bn, precision=precision, x1_s2=True)
         y, part = r if want_bn else (r, None)
-        ctx.cfg = (stride, pad, act, slope, precision)
+        ctx.cfg = (stride, pad, act, slope, precision, wgrad_s2)
         ctx.save_for_backward(x1, x2, weight, y if act != ACT_NONE else None)
         ctx.has_bias = bias is not None
         ctx.has_res = res is not None
@@ -628,9 +643,9 @@ class _Conv2d(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy, _=None):
         if dy is None:
-            return (None,) * 11
+            return (None,) * 12
         x1, x2, weight, y = ctx.saved_tensors
-        stride, pad, act, slope, precision = ctx.cfg
+        stride, pad, act, slope, precision, wgrad_s2 = ctx.cfg
         dy = to_nhwc(dy)
         if act != ACT_NONE:
             dy = _act_bwd(y, dy, act, slope)
@@ -641,14 +656,15 @@ class _Conv2d(torch.autograd.Function):
         if x2 is not None and ctx.needs_input_grad[1]:
             dx2 = _conv_dgrad_impl(dy, weight, stride, pad, h, w, c1, c1 + x2.shape[1], precision=precision, x1_s2=True)
         if ctx.needs_input_grad[2]:
-            dw = _conv_wgrad_impl(x1, x2, dy, weight.shape, stride, pad, precision=precision)
+            dw = _conv_wgrad_impl(x1, x2, dy, weight.shape, stride, pad, precision=precision, wgrad_s2=wgrad_s2)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             db = _channel_sum(dy, weight.shape[0])
         dres = dy if (ctx.has_res and ctx.needs_input_grad[8]) else None      # residual joins before the activation
-        return dx1, dx2, dw, db, None, None, None, None, dres, None, None
+        return dx1, dx2, dw, db, None, None, None, None, dres, None, None, None
 
 
-def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, x2=None, res=None, bn_stats=False, precision='fp32'):
+def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, x2=None, res=None, bn_stats=False, precision='fp32',
+           wgrad_s2='fp32'):
     """F.conv2d on the HIP kernels.  `padding`: int or (top, bottom, left, right) (TF-"same" static
     padding of the EfficientNet convs is asymmetric); `x2`: second tensor concatenated after x;
     `res`: tensor added in the epilogue before the activation (act(conv(x) + bias + res)).
@@ -656,12 +672,15 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, x
     this shape's kernel has none); hand it to batch_norm_act(y, bn, stats_part=part) to skip its statistics pass.
     `precision='bf16x1'` (opt-in, an approximation: both operands rounded once to bf16, fp32 accumulation): a 3x3 pad-1 conv of
     stride 1 or 2 asks the one-term kernels first, in the forward and in each of its gradients, and runs today's kernel wherever
-    their predicates refuse -- it never raises for a shape; `part` of a routed forward is empty.  'fp32' (default): today's launches."""
+    their predicates refuse -- it never raises for a shape; `part` of a routed forward is empty.  'fp32' (default): today's launches.
+    `wgrad_s2='bf16x1'` (opt-in beside precision='bf16x1', ValueError otherwise): the weight gradient of a 3x3 stride-2 pad-1 conv
+    asks the one-term stride-2 kernel first as well; 'fp32' (default) leaves it on today's kernel."""
     _lib.require_gpu(x)
     if precision not in _PRECISIONS:
         raise ValueError('conv2d: unknown precision %r (one of %s)' % (precision, ', '.join(_PRECISIONS)))
+    _check_wgrad_s2('conv2d', precision, wgrad_s2)
     pad = tuple(int(v) for v in padding) if isinstance(padding, (tuple, list)) else int(padding)
-    y, part = _Conv2d.apply(x, x2, weight, bias, int(stride), pad, int(act), float(slope), res, bool(bn_stats), precision)
+    y, part = _Conv2d.apply(x, x2, weight, bias, int(stride), pad, int(act), float(slope), res, bool(bn_stats), precision, wgrad_s2)
     return (y, part) if bn_stats else y
 
 
@@ -809,13 +828,34 @@ class train_precision(_precision):
     rounded once to bf16 (fp32 accumulation, fp32 tensors: an approximation) wherever the kernels' predicates hold, and stay on the
     fp32-class kernels elsewhere.  models_seg_gan.ConvolutionalBlock (the discriminator) hands the mode to conv2d(precision=), whose
     node also has the stride-2 routes.  'fp32' (the default) launches exactly what runs without the context.  A node reads the mode in
-    its forward and keeps it: its backward uses the forward's mode whatever is set when .backward() runs."""
+    its forward and keeps it: its backward uses the forward's mode whatever is set when .backward() runs.
+    wgrad_s2='bf16x1' (a second switch, default 'fp32', only beside mode 'bf16x1'): ConvolutionalBlock also hands this on, and the
+    weight gradient of its stride-2 convs asks wgrad_s2_k32_x1_kernel first.  The block nodes do not read it."""
     _state = ['fp32']
+    _s2_state = ['fp32']
+
+    def __init__(self, mode, wgrad_s2='fp32'):
+        super(train_precision, self).__init__(mode)
+        _check_wgrad_s2('train_precision', mode, wgrad_s2)
+        self.wgrad_s2 = wgrad_s2
+
+    def __enter__(self):
+        self.prev_s2 = self._s2_state[0]; self._s2_state[0] = self.wgrad_s2
+        return super(train_precision, self).__enter__()
+
+    def __exit__(self, *a):
+        self._s2_state[0] = self.prev_s2
+        return super(train_precision, self).__exit__(*a)
 
 
 def train_precision_mode():
     """The mode the innermost `train_precision` block set ('fp32' outside any)."""
     return train_precision._state[0]
+
+
+def train_wgrad_s2_mode():
+    """The wgrad_s2 switch the innermost `train_precision` block set ('fp32' outside any)."""
+    return train_precision._s2_state[0]
 
 
 def _conv_wgrad_bf16x1_impl(x1, x2, dy, weight_shape):
@@ -834,6 +874,31 @@ def _conv_wgrad_bf16x1_impl(x1, x2, dy, weight_shape):
     ws = _ws(call('ssg_conv2d_wgrad_bf16x1_workspace_bytes', C.byref(d)), dy.device)
     d.ws = ws.data_ptr(); d.ws_bytes = ws.numel() * 8
     _timed_call(_WGRAD_X1_KIND, 'ssg_conv2d_wgrad_bf16x1_f32', d, (), (n, h, w, i, o, 3, 1), 2.0 * n * h * w * o * i * 9)
+    return dw
+
+
+# csrc/conv_wgrad_s2_k32_x1.hip: the stride-2 form, behind a switch of its own (wgrad_s2).  Labels in a table of their own.
+_WGRAD_X1_S2_LABELS = {81: 'wgrad_s2_k32_x1_kernel<128>', 82: 'wgrad_s2_k32_x1_kernel<64>'}
+_WGRAD_X1_S2_KIND = (_WGRAD_X1_S2_LABELS, 'ssg_conv2d_wgrad_bf16x1_s2_kernel_id', _WGRAD_SHAPE)
+
+
+def _conv_wgrad_s2_bf16x1_impl(x, dy, weight_shape):
+    """Weight gradient [O, I, 3, 3] of the 3x3 stride-2 pad-1 conv of x with x and dy rounded once to bf16
+    (ssg_conv2d_wgrad_bf16x1_s2_f32).  Returns None, with nothing launched, where ssg_conv2d_wgrad_bf16x1_s2_ok refuses: the
+    caller then takes _conv_wgrad_impl's fp32-class kernel for this launch."""
+    o, i, kh, kw = weight_shape
+    n, c, h, w = x.shape
+    if (kh, kw) != (3, 3) or c != i or tuple(dy.shape) != (n, o, (h + 1) // 2, (w + 1) // 2):
+        return None
+    d = _wgrad_desc(x, c, None, 0, dy, weight_shape, 2, _X1_TAPS)
+    if not call('ssg_conv2d_wgrad_bf16x1_s2_ok', C.byref(d)):
+        return None
+    oh, ow = dy.shape[2], dy.shape[3]
+    dw = torch.empty((o, i, 3, 3), device=dy.device, dtype=torch.float32)
+    d.dw_oihw = dw.data_ptr()
+    ws = _ws(call('ssg_conv2d_wgrad_bf16x1_s2_workspace_bytes', C.byref(d)), dy.device)
+    d.ws = ws.data_ptr(); d.ws_bytes = ws.numel() * 8
+    _timed_call(_WGRAD_X1_S2_KIND, 'ssg_conv2d_wgrad_bf16x1_s2_f32', d, (), (n, oh, ow, i, o, 3, 2), 2.0 * n * oh * ow * o * i * 9)
     return dw
 
 
@@ -867,7 +932,8 @@ def _conv_dgrad_bf16x1_impl(dy, weight, h, w, c_lo, c_hi, res=None):
 # ----------------------------------------------------------------------------- opt-in bf16x1: the stride-2 conv of the single-conv node
 # csrc/conv_s2_k32_x1.hip: the 3x3 stride-2 pad-1 forward (ssg_conv2d_bf16x1_s2_f32) and its input gradient as four parity-class
 # launches (ssg_conv2d_bf16x1_cls_f32; the tap lists are those of the per-class launches of _conv_dgrad_impl).  Reached only from
-# _Conv2d under precision='bf16x1'; the stride-2 weight gradient stays on the fp32-class kernel.  Labels in tables of their own.
+# _Conv2d under precision='bf16x1'; the stride-2 weight gradient stays on the fp32-class kernel unless wgrad_s2='bf16x1' asks for
+# _conv_wgrad_s2_bf16x1_impl above.  Labels in tables of their own.
 _X1_S2_LABELS = {73: 'conv_s2_k32_x1_kernel<128,9>', 74: 'conv_s2_k32_x1_kernel<64,9>'}
 _X1_CLS_LABELS = {75: 'conv_s2_k32_x1_kernel<128,1>', 76: 'conv_s2_k32_x1_kernel<64,1>', 77: 'conv_s2_k32_x1_kernel<128,2>',
                   78: 'conv_s2_k32_x1_kernel<64,2>', 79: 'conv_s2_k32_x1_kernel<128,4>', 80: 'conv_s2_k32_x1_kernel<64,4>'}
@@ -971,21 +1037,23 @@ def _conv_dgrad_s2_bf16x1_impl(dy, weight, h, w, c_lo, c_hi, out=None):
     return dx
 
 
-def conv2d_bf16x1_train(x, weight, bias=None, act=ACT_NONE, slope=0.0, x2=None, res=None, stride=1):
+def conv2d_bf16x1_train(x, weight, bias=None, act=ACT_NONE, slope=0.0, x2=None, res=None, stride=1, wgrad_s2='fp32'):
     """The differentiable form of `conv2d_bf16x1`: forward on conv_halo_k32_x1_kernel, gradients for x, x2 and res on the same
     kernel (dy and the transposed weight rounded to bf16), weight gradient on wgrad_k32_x1_kernel (x and dy rounded), bias gradient
     by the fp32 channel sum.  A gradient whose own predicate refuses (a 32-channel slice, say) runs on the fp32-class kernel.
     stride=2 (no x2 / res): forward and input gradient on conv_s2_k32_x1_kernel where `conv2d_bf16x1_s2_ok` holds, the weight
-    gradient on the fp32-class kernel.  Raises ValueError where `conv2d_bf16x1_ok` / `conv2d_bf16x1_s2_ok` is false; there is no
+    gradient on the fp32-class kernel, or with wgrad_s2='bf16x1' on wgrad_s2_k32_x1_kernel where its predicate holds.  Raises
+    ValueError where `conv2d_bf16x1_ok` / `conv2d_bf16x1_s2_ok` is false or wgrad_s2 is neither 'fp32' nor 'bf16x1'; there is no
     CPU fallback."""
     for t in (x, weight, bias, x2, res):
         if t is not None:
             _lib.require_gpu(t)
+    _check_wgrad_s2('conv2d_bf16x1_train', 'bf16x1', wgrad_s2)
     if stride == 2:
         if x2 is not None or res is not None or not conv2d_bf16x1_s2_ok(x, weight):
             raise ValueError('conv2d_bf16x1_train: no stride-2 bf16x1 kernel for x %s weight %s%s (conv2d_bf16x1_s2_ok is False)' % (
                 tuple(x.shape), tuple(weight.shape), ' with x2 / res' if (x2 is not None or res is not None) else ''))
-        return _Conv2d.apply(x, None, weight, bias, 2, 1, int(act), float(slope), None, False, 'bf16x1')[0]
+        return _Conv2d.apply(x, None, weight, bias, 2, 1, int(act), float(slope), None, False, 'bf16x1', wgrad_s2)[0]
     if stride != 1:
         raise ValueError('conv2d_bf16x1_train: stride %r (1 or 2)' % (stride,))
     if not conv2d_bf16x1_ok(x, weight, x2=x2, res=res):

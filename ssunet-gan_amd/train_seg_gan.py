@@ -88,16 +88,20 @@ class _params_frozen(object):
 
 
 def gan_step(input, target, generator, discriminator, criterion, adversarial_loss_criterion, content_loss_criterion,
-             optimizer_g, optimizer_d, num_class, sync_g=None, sync_d=None, precision='fp32', d_precision='fp32'):
+             optimizer_g, optimizer_d, num_class, sync_g=None, sync_d=None, precision='fp32', d_precision='fp32',
+             d_wgrad_s2='fp32'):
     """One iteration of train_seg_gan.py:182-233.  Returns device scalars (loss, iou, dice, closs, adv_g, adv_d).
     precision: 'fp32' (default) or 'bf16x1' -- ops.train_precision around the GENERATOR's forward and the backward that reaches
     it (its BasicBlocks then run their 3x3 convs with bf16 operands and fp32 accumulation); the discriminator, the losses, the
     parameters, the gradients and the optimizer state stay fp32 in either mode.
     d_precision: the same choice for the DISCRIMINATOR -- ops.train_precision around its three forwards (its conv nodes keep the
     mode for their backward): the 3x3 convs of its ConvolutionalBlocks then ask the one-term kernels first, stride 1 and stride 2,
-    and run today's kernels where those refuse (the 3 -> 64 stem, narrow levels, the stride-2 weight gradient, spectral norm)."""
+    and run today's kernels where those refuse (the 3 -> 64 stem, narrow levels, the stride-2 weight gradient, spectral norm).
+    d_wgrad_s2: 'fp32' (default) or 'bf16x1' -- a second switch, legal only beside d_precision='bf16x1' (ValueError otherwise, before
+    anything runs): the weight gradient of the discriminator's 3x3 stride-2 convs asks the one-term wgrad_s2_k32_x1_kernel first."""
     if d_precision not in ops._PRECISIONS:
         raise ValueError('gan_step: unknown d_precision %r (one of %s)' % (d_precision, ', '.join(ops._PRECISIONS)))
+    ops._check_wgrad_s2('gan_step', d_precision, d_wgrad_s2)
     with _stage('ssg.G_forward'), ops.train_precision(precision):
         generator_output = generator(input)                                    # :188
         generator_output = ops.nan_to_zero_(generator_output)                  # :190
@@ -119,7 +123,7 @@ def gan_step(input, target, generator, discriminator, criterion, adversarial_los
     # the generator and optimizer_d.zero_grad() (:225) clears them before anything reads them.  They are computed
     # all the same (the step does the reference's work); SSG_ELIDE_DEAD_D_GRADS=1 leaves them out (identical
     # results, -2.6 % step time at bs16/512^2 -- DESIGN.md) and bench.py then says so in its JSON line.
-    with _params_frozen(discriminator, ELIDE_DEAD_D_GRADS), ops.train_precision(d_precision):
+    with _params_frozen(discriminator, ELIDE_DEAD_D_GRADS), ops.train_precision(d_precision, wgrad_s2=d_wgrad_s2):
         seg_discriminated = discriminator(generator_output)                    # :202
     adversarial_loss = _adv_loss(adversarial_loss_criterion, seg_discriminated, 1.0)
     perceptual_loss = loss + ALPA * content_loss + BETA * adversarial_loss     # :205
@@ -137,7 +141,7 @@ def gan_step(input, target, generator, discriminator, criterion, adversarial_los
     with _stage('ssg.G_optimizer'):
         _step_optimizer(optimizer_g, GRAD_CLIP)                                # :211-215
 
-    with _stage('ssg.D_forward_2_3'), ops.train_precision(d_precision):
+    with _stage('ssg.D_forward_2_3'), ops.train_precision(d_precision, wgrad_s2=d_wgrad_s2):
         hr_discriminated = discriminator(target)                               # :217
         sr_discriminated = discriminator(generator_output.detach())            # :218
         adversarial_loss = _adv_loss(adversarial_loss_criterion, sr_discriminated, 0.0) + \
@@ -171,7 +175,8 @@ def train(epoch, config, train_loader, generator, discriminator, criterion, adve
         loss, iou, dice, _, _, _ = gan_step(input, target, generator, discriminator, criterion,
                                              adversarial_loss_criterion, content_loss_criterion, optimizer_g, optimizer_d,
                                              num_class, sync_g, sync_d, precision=config.get('precision', 'fp32'),
-                                             d_precision=config.get('d_precision', 'fp32'))
+                                             d_precision=config.get('d_precision', 'fp32'),
+                                             d_wgrad_s2=config.get('d_wgrad_s2', 'fp32'))
         n = input.size(0)
         avg_meters['loss'].update(loss, n)
         avg_meters['iou'].update(iou, n)
