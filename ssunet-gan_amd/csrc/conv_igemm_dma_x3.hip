@@ -6,6 +6,8 @@
 //     whose tap falls outside the image carries an out-of-range offset and receives zeros); split in registers after the
 //     fragment read.  B tile = the pre-split weights of the step, [BN rows][96 B] (mfma_split.h), 12 / 6 contiguous KiB.
 //   * wave layout 4 x 1 (one activation split per pixel row group), 3 stages, two K-steps in flight across the one barrier per step.
+// Since DESIGN.md 3.20 this kernel is the fallback body: ssg_conv_igemm_dma_x3_launch runs the split-once body of
+// conv_igemm_dma_k32.hip (same plan, kernel id, label, tiles, pack and bnpart rows) wherever ssg_conv_dma_k32_ok holds.
 #include "common.h"
 #include "lds_dma.h"
 #include "conv_args.h"
@@ -212,6 +214,32 @@ int ssg_conv_dma_x3_bn(const ConvArgs& a) {
   return 0;
 }
 
+// conv_igemm_dma_k32.hip: the split-once body (32-channel steps on v_mfma_f32_16x16x32_bf16); same tiles, pack and bnpart rows
+bool ssg_conv_dma_k32_ok(const ConvArgs& a);
+int ssg_conv_igemm_dma_k32_launch(const ConvArgs& a, int bn, hipStream_t st);
+
+// Which body a launch of this family runs: the split-once body (2) wherever its preconditions hold, else conv_igemm_dma_x3_kernel (1)
+int ssg_conv_dma_split_body(const ConvArgs& a) { return ssg_conv_dma_k32_ok(a) ? 2 : 1; }
+
 int ssg_conv_igemm_dma_x3_launch(const ConvArgs& a, hipStream_t st) {
-  return ssg_conv_dma_x3_bn(a) == 128 ? launch<128>(a, st) : launch<64>(a, st);
+  const int bn = ssg_conv_dma_x3_bn(a);
+  if (ssg_conv_dma_split_body(a) == 2) return ssg_conv_igemm_dma_k32_launch(a, bn, st);
+  return bn == 128 ? launch<128>(a, st) : launch<64>(a, st);
+}
+
+// Diagnostic, outside the ABI of include/ssunet_hip.h (tests/test_conv_dma_body.py): which body ssg_conv2d_f32 runs for a descriptor
+// of the LDS-DMA family (1x1, stride 2, parity classes on whole 64- / 128-column tiles) -- 2 = the split-once body of
+// conv_igemm_dma_k32.hip, 1 = not that one: conv_igemm_dma_x3_kernel under kernel id 50 / 51, or, for a descriptor without a split
+// pack (what SSG_MFMA_SPLIT=0 sends), the fp32 kernel of ids 20-22; 0 = the descriptor does not validate or belongs to another family.
+extern "C" int ssg_conv_dma_body(const ssg_conv_desc* d) {
+  if (!d) return 0;
+  const int id = ssg_conv2d_kernel_id(d);
+  if (id >= 20 && id <= 22) return (ssg_conv2d_split_bn(d) == 64 || ssg_conv2d_split_bn(d) == 128) ? 1 : 0;
+  if (id != 50 && id != 51) return 0;
+  ConvArgs a{};                                          // the fields the family's predicates read, as conv_igemm.hip fills them
+  a.in1 = d->in1; a.in2 = d->C2 ? d->in2 : d->in1; a.w = (const float*)d->w_split; a.w32 = d->w; a.bias = d->bias; a.res = d->res; a.out = d->out;
+  a.C1 = d->C1; a.C2 = d->C2; a.ld1 = d->ld1; a.ld2 = d->C2 ? d->ld2 : d->ld1;
+  a.N = d->N; a.H = d->H; a.W = d->W; a.Kp = d->Kp; a.kmode = d->kmode; a.ldr = d->ldr; a.Cout = d->Cout; a.ldo = d->ldo;
+  a.GH = d->GH; a.GW = d->GW; a.ntaps = d->ntaps; a.nsteps = d->Kp / 16;
+  return ssg_conv_dma_split_body(a);
 }
