@@ -105,11 +105,14 @@ typedef struct {
  * out, results agree with the fp32-MFMA kernel to fp32 accumulation accuracy (tests/test_split_gpu.py), at 16/6 of its
  * matrix rate.  ssg_conv2d_split_bn: 0 when the launch for `d` has no split-operand kernel, else the column tile (64 / 128)
  * its weights must be split for: `w_split` = ssg_pack_weights_split_bf16x3(d->w rows [R][Kp] in kmode 0, R, Kp, BN) --
- * ssg_pack_weights_split_bytes bytes, layout [ceil(R/BN)][Kp/16][BN][96 B].
+ * ssg_pack_weights_split_bytes bytes, layout [ceil(R/BN)][Kp/16][BN][96 B]: the 96 bytes of a row and 16-channel K-step are six
+ * 16-byte slots, bf16 term p (0..2) of channels 8h .. 8h+7 of the step in slot (2p + h) ^ ((row >> 3) & 1); rows beyond R are zeros.
  * ABI 7 (round 4): ssg_conv2d_split_bn may also return 1128 or 1064 -- the launch goes to the 32-channel-chunk kernel on
  * v_mfma_f32_16x16x32_bf16 (conv_igemm_halo_k32.hip: 8 x 32-pixel x 128-channel tiles of 512 threads, or 4 x 32 x 64 of 256), whose
  * weights are packed by the same two functions with BN = that code: layout [R/bn][Kp/32 steps = chunk32 * 9 + tap][bn/16
- * fragments][3 planes][64 lanes][16 B] (bn = code - 1000; R % bn == 0, Kp % 288 == 0).  The value is always the pack format the
+ * fragments][3 planes][64 lanes][16 B] (bn = code - 1000; R % bn == 0, Kp % 288 == 0; lane l of fragment j holds bf16 term `plane` of row
+ * j*16 + (l & 15), channels chunk32*32 + (l >> 4)*8 .. +7; 1016 / 1032, for Cout 12..16 / 17..32: R <= bn, one tile padded with zero
+ * rows).  The value is always the pack format the
  * launch reads, whichever kernel reads it (the 16 x 32-pixel x 64-channel tiles of 512 threads read the pack of 1064;
  * ssg_conv2d_kernel_id tells the kernels apart).  ssg_conv_set_k32_mode(0 / 1 / 2): never /
  * where the grid fills the chip (default, SSG_K32) / wherever the shape is legal (tests). */
