@@ -307,8 +307,12 @@ int ssg_linear_wgrad_f32(const float* x, int n, int k, int ldx, const float* dy,
  * v_mfma_f32_32x32x16_bf16, fp32 accumulation.  bf16 activations are NHWC-with-stride tensors of 16-bit elements whose
  * channel count and pixel stride are multiples of 8 (16-byte rows).  Weights stay fp32 in the module; per use they are
  * packed to bf16 rows [rows_pad][Kp] (rows_pad % 128 == 0, Kp % 32 == 0, zero padded): transpose 0 = [O][I] for the
- * forward, transpose 1 = [I][O] for the input gradient.
+ * forward, transpose 1 = [I][O] for the input gradient.  ssg_pack_weights_bf16 rounds to nearest even and writes all
+ * rows_pad x Kp elements: +0 in every row past the matrix and in columns [cols, Kp) of every row.
  *   ssg_gemm_bf16        out[p][n] = sum_k x[p][k] * w[n][k] (+ res[p][n]), out/res bf16      (forward and dgrad)
+ *                        w_packed: N rows of stride Kp (Kp >= K); columns [K, round32(K)) must be zero (the pack's
+ *                        padding), rows >= N are never read.  x, res and out are read / written in channels [0, K) /
+ *                        [0, N) only, whatever ldx, ldr, ldo.  res == NULL: no residual, ldr is ignored (any value).
  *   ssg_gemm_wgrad_bf16  dw[m][n]  = sum_p dy[p][m] * x[p][n], fp32 [M][N] (= OIHW of a 1x1 conv); split-K over pixels
  *                        with fp32 slabs in `ws` and an ordered reduce (bitwise reproducible) */
 int ssg_pack_weights_bf16(const float* w, int O, int I, int transpose, int rows_pad, int Kp, void* out, void* stream);
@@ -322,7 +326,9 @@ int ssg_gemm_wgrad_bf16(const void* dy, int ldd, const void* x, int ldx, int64_t
  * TF-SAME padding utils.py:123-146): SURVEY.md 8(b) `conv2d_{fwd,dgrad,wgrad}_nhwc_bf16`, k = 3.  x: fp32 NHWC image with 4-channel pixel
  * rows (the model input); image values and weights are rounded to bf16 before they multiply, fp32 accumulation, bf16 output [N, OH, OW, Cout]
  * (Cout % 8 == 0).  w_oihw / dw_oihw: fp32 [Cout][Cin][KH][KW].  wgrad: ws of ssg_conv2d_thin_bf16_wgrad_workspace_bytes bytes.
- * dgrad writes the fp32 image gradient [N, H, W, 4] (channels >= Cin: zeros). */
+ * dgrad writes the fp32 image gradient as 4-float pixels of stride lddx: channels [0, Cin) the gradient, channels [Cin, 4) zeros,
+ * lanes [4, lddx) untouched.  The forward and the weight gradient load all 4 floats of an image pixel (channels [Cin, 4) must be
+ * finite: they meet zero weights / are dropped) and nothing of lanes [4, ldx). */
 int ssg_conv2d_thin_bf16(const float* x, int N, int H, int W, int ldx, const float* w_oihw, int Cout, int Cin, int KH, int KW,
                          int stride, int pad_t, int pad_l, int OH, int OW, void* y, int ldy, void* stream);
 int64_t ssg_conv2d_thin_bf16_wgrad_workspace_bytes(int N, int OH, int OW, int Cout, int KH, int KW);
