@@ -656,6 +656,24 @@ int ssg_sw_gather_patches_u8_f32(const uint8_t* img, int H, int W, const int32_t
 int ssg_sw_merge_masks_f32_u8(const float* probs, int ld, int P, int C, int S, const int32_t* org, const int32_t* org_host,
                               const int32_t* weight, int p_size, int H, int W, uint8_t* out, void* stream);
 
+/* The ground-truth branch of the same pipeline (mask_convert and the evaluation of the two mask sets,
+ * aerial_image_segmentation_api.py:220-236,394-406): every value is an integer, so both are exact.
+ *
+ * ssg_sw_gather_labels_u8_f32 (api.py:220-236,394-406): label is [H][W][3] uint8 (BGR label image, 4-byte aligned), origins as
+ * above; out is [P, C, out_size, out_size] fp32 NHWC with ld = 4, 1 <= C <= 3, holding 0.0f or 1.0f -- mask_convert(patch, c,
+ * out_size) / 255.0 for c < C -- and +0.0f in the lanes C .. 3.  A pixel selects class 0 / 1 / 2 when its three bytes, in memory
+ * order, are (255, 255, 255) / (255, 0, 0) / (0, 0, 255).  p_size / out_size = 1: the selection itself; = 2: at least 2 of the
+ * 2 x 2 box selected (resize_u8 at 1/2 gives (255 k + 2) >> 2 in {0, 64, 128, 191, 255}; post_process_resized_mask sends 64 to
+ * 0 and 128, 191 to 255).
+ *
+ * ssg_sw_mask_counts_u8 (api.py:394-406, the two mask lists it returns): pred and gt are [C][HW] uint8 (any alignment);
+ * counts is uint64 [C][3] on the device, 8-byte aligned, zeroed by the caller before the first call: the entry ADDS, per class,
+ * the number of pixels with pred > 127 and gt > 127, with pred > 127, and with gt > 127.  Integer sums combined with 64-bit
+ * integer atomics: exact and independent of the order. */
+int ssg_sw_gather_labels_u8_f32(const uint8_t* label, int H, int W, const int32_t* org, const int32_t* org_host, int P,
+                                int p_size, int out_size, int C, float* out, void* stream);
+int ssg_sw_mask_counts_u8(const uint8_t* pred, const uint8_t* gt, int C, int64_t HW, uint64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

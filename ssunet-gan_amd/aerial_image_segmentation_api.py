@@ -5,7 +5,10 @@ GPU side: the eval-mode generator forward over all patches of an image.  The ref
 (`api.py:385-390`); here patches are batched and every BasicBlock runs as three MFMA launches with its batch norms folded
 in, then one sigmoid kernel -- same values, no per-patch sync.  `segment_image` also runs the two host loops around the
 forwards (patch cutting / resizing / normalisation, and `patch_merge`) as HIP kernels, bit for bit what the host functions
-below compute; those stay as the oracle and for the ground-truth branch.
+below compute; those stay as the oracle.  With a label image it runs the ground-truth branch (`mask_convert` per patch and class,
+a second `patch_merge`, `api.py:220-236,394-406`) on the device too, and `evaluate_image` / `evaluate_images` reduce the two mask
+sets to per-class pixel counts (IoU, Dice) there, without downloading a mask.  The overlay JPGs (`save_masking*`), PNG decoding,
+non-square inference sizes and resize factors other than 1 and 2 are not covered.
 
 Host side (numpy, no cv2 / albumentations -- neither is installed here, and the package takes on no host dependency for
 them): `load_segmentation_models` (`api.py:302-333`), `get_patched_input` (`api.py:336-373`, including its double
@@ -282,7 +285,44 @@ def unique_origins(org):
     return list(count.keys()), list(count.values())
 
 
-def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_probs=False, precision='fp32'):
+def _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, who):
+    """The device half of `segment_image` / `evaluate_image`: (prediction masks [C, H, W] uint8 on the device, ground-truth masks
+    likewise or None, probabilities, origins, weights).  Every check runs before the first upload or launch."""
+    p_size, size, overlap, classes = config['patch_size'], config['input_w'], config['patch_overlap'], config['num_classes']
+    if (config['input_h'], config['input_w']) != (size, size):
+        raise NotImplementedError('non-square inference size')
+    img_bgr = np.asarray(img_bgr)
+    if img_bgr.dtype != np.uint8 or img_bgr.ndim != 3 or img_bgr.shape[2] != 3:
+        raise TypeError('%s expects an HxWx3 uint8 image' % who)
+    if label_bgr is not None:
+        label_bgr = np.asarray(label_bgr)
+        if label_bgr.dtype != np.uint8:
+            raise TypeError('%s expects a uint8 label image' % who)
+        if label_bgr.shape != img_bgr.shape:
+            raise ValueError('%s: the label image is %s, the image %s' % (who, label_bgr.shape, img_bgr.shape))
+        if not 1 <= classes <= 3:
+            raise ValueError('%s: %d classes: the label palette (mask_convert) has 3 colours' % (who, classes))
+    img_h, img_w = img_bgr.shape[0], img_bgr.shape[1]
+    org = patch_origins(img_h, img_w, p_size, overlap)
+    org, weights = unique_origins(org) if dedupe else (org, [1] * len(org))
+    dev = next(model.parameters()).device
+    img = torch.from_numpy(np.ascontiguousarray(img_bgr)).to(dev)
+    probs = ops.new_nhwc(len(org), classes, size, size, dev)
+    model.eval()
+    gt_masks = None
+    with torch.no_grad(), ops.infer_precision(precision):
+        for i in range(0, len(org), batch_size):
+            x = ops.sw_gather_patches(img, org[i:i + batch_size], p_size, size)
+            ops.sigmoid_into(model(x), probs[i:i + batch_size])
+        masks = ops.sw_merge_masks(probs, org, weights, p_size, img_h, img_w)
+        if label_bgr is not None:                        # api.py:394-406: mask_convert per patch and class, then patch_merge
+            label = torch.from_numpy(np.ascontiguousarray(label_bgr)).to(dev)
+            gt = ops.sw_gather_labels(label, org, p_size, size, classes)
+            gt_masks = ops.sw_merge_masks(gt, org, weights, p_size, img_h, img_w)
+    return masks, gt_masks, probs, org, weights
+
+
+def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_probs=False, precision='fp32', label_bgr=None):
     """`segmentation_inference_full(model, *get_patched_input(...), config, False)[0]` for an image already in memory, with
     everything between the uint8 image and the uint8 masks on the device: the image is uploaded once, each batch of patches is
     cut, resized and normalised by `ops.sw_gather_patches`, `sigmoid(model(x))` stays on the device, `ops.sw_merge_masks` does
@@ -292,30 +332,56 @@ def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_pro
     `return_probs`: also return (the host copy [P, C, S, S] of the probabilities that were merged, their origins, their weights).
     `precision`: 'fp32' (default, unchanged) or 'bf16x1', the approximation described at `infer_patches` (bf16 operand rounding in
     the BasicBlock 3x3 stride-1 convs); masks can differ from the fp32 path where a probability is near the threshold.
-    Not covered, as on the host path they stay with: the ground-truth branch, PNG decoding, non-square inference sizes and
-    resize factors other than 1 and 2."""
-    p_size, size, overlap, classes = config['patch_size'], config['input_w'], config['patch_overlap'], config['num_classes']
-    if (config['input_h'], config['input_w']) != (size, size):
-        raise NotImplementedError('non-square inference size')
-    img_bgr = np.asarray(img_bgr)
-    if img_bgr.dtype != np.uint8 or img_bgr.ndim != 3 or img_bgr.shape[2] != 3:
-        raise TypeError('segment_image expects an HxWx3 uint8 image')
-    img_h, img_w = img_bgr.shape[0], img_bgr.shape[1]
-    org = patch_origins(img_h, img_w, p_size, overlap)
-    org, weights = unique_origins(org) if dedupe else (org, [1] * len(org))
-    dev = next(model.parameters()).device
-    img = torch.from_numpy(np.ascontiguousarray(img_bgr)).to(dev)
-    probs = ops.new_nhwc(len(org), classes, size, size, dev)
-    model.eval()
-    with torch.no_grad(), ops.infer_precision(precision):
-        for i in range(0, len(org), batch_size):
-            x = ops.sw_gather_patches(img, org[i:i + batch_size], p_size, size)
-            ops.sigmoid_into(model(x), probs[i:i + batch_size])
-        masks = ops.sw_merge_masks(probs, org, weights, p_size, img_h, img_w).cpu().numpy()
+    `label_bgr`: the BGR label image of `img_bgr` (same shape, uint8) -- the ground-truth branch (`gt_mask_flag=True`, api.py:394-406)
+    on the device: the label is uploaded once, `ops.sw_gather_labels` does `mask_convert` for every patch and class at the same
+    origins, the same `ops.sw_merge_masks` merges them with the same weights, and the result becomes (masks, gt_masks) -- both
+    lists of `segmentation_inference_full(..., gt_mask_flag=True)`, followed by the three `return_probs` items if asked for.  The
+    ground-truth masks are integer arithmetic on the label alone: they depend on neither `dedupe` nor `precision`.  A label of
+    another shape raises ValueError; num_classes above 3 raises ValueError (`mask_convert` has no colour for them).
+    Not covered, as on the host path they stay with: the overlay JPGs, PNG decoding, non-square inference sizes and resize
+    factors other than 1 and 2.  `evaluate_image` / `evaluate_images` turn the two mask sets into counts without a download."""
+    classes = config['num_classes']
+    masks, gt_masks, probs, org, weights = _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, 'segment_image')
+    masks = masks.cpu().numpy()
     masks = [masks[c] for c in range(classes)]
+    out = (masks,)
+    if label_bgr is not None:
+        gt_masks = gt_masks.cpu().numpy()
+        out += ([gt_masks[c] for c in range(classes)],)
     if return_probs:
-        return masks, probs.cpu().contiguous().numpy(), org, weights
-    return masks
+        out += (probs.cpu().contiguous().numpy(), org, weights)
+    return out if len(out) > 1 else masks
+
+
+def evaluate_image(model, img_bgr, label_bgr, config, batch_size=12, dedupe=True, precision='fp32', counts=None):
+    """`segment_image(..., label_bgr=label_bgr)` with both mask sets kept on the device and reduced there by
+    `ops.sw_mask_counts`: returns an int64 [num_classes, 3] DEVICE tensor of pixel counts per class -- (prediction and ground
+    truth, prediction, ground truth) -- added into `counts` if such a tensor is given.  No mask is downloaded and nothing
+    synchronises; read the tensor (`.cpu()`) when the numbers are needed."""
+    if label_bgr is None:
+        raise TypeError('evaluate_image needs a label image')
+    masks, gt_masks, _, _, _ = _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, 'evaluate_image')
+    return ops.sw_mask_counts(masks, gt_masks, out=counts)
+
+
+def evaluate_images(model, pairs, config, batch_size=12, dedupe=True, precision='fp32'):
+    """`evaluate_image` over `pairs`, an iterable of (image, label), each an HxWx3 uint8 BGR array or a path read with
+    `imread_bgr`; the counts accumulate on the device and are read once at the end.  Returns a dict: `counts`, a numpy int64
+    [num_classes, 3] of (intersection I, prediction P, ground truth G) pixels per class over all images, and per class the
+    Python floats `iou` = (I + 1e-5) / (P + G - I + 1e-5) and `dice` = (2 I + 1e-5) / (P + G + 1e-5) -- the smoothing of
+    `metrics.iou_score`."""
+    counts = None
+    for image, label in pairs:
+        image = imread_bgr(image) if isinstance(image, (str, os.PathLike)) else image
+        label = imread_bgr(label) if isinstance(label, (str, os.PathLike)) else label
+        counts = evaluate_image(model, image, label, config, batch_size, dedupe, precision, counts)
+    if counts is None:
+        raise ValueError('evaluate_images: no (image, label) pair given')
+    counts = counts.cpu().numpy()
+    smooth = 1e-5
+    iou = [float((i + smooth) / (p + g - i + smooth)) for i, p, g in counts.tolist()]
+    dice = [float((2 * i + smooth) / (p + g + smooth)) for i, p, g in counts.tolist()]
+    return dict(counts=counts, iou=iou, dice=dice)
 
 
 def load_segmentation_models(config_file):

@@ -1,9 +1,12 @@
 // Sliding-window inference around the generator forward (aerial_image_segmentation_api.py, BASELINE config 5), HBM-bound:
 //   sw_gather_kernel: uint8 BGR image + patch origins -> network input (crop, 2x2 box resize, double normalisation), NHWC ld 4;
 //   sw_merge_kernel:  per-patch probabilities -> {0, 255} class masks at image resolution (uint8 round trip, 2x bilinear,
-//                     threshold, overlap vote, threshold).
-// Both restate integer / single-rounding arithmetic of the host functions get_patched_input and patch_merge and are meant
-// to match them bit for bit.  ABI: include/ssunet_hip.h.
+//                     threshold, overlap vote, threshold);
+//   sw_gather_labels_kernel: uint8 BGR label image + patch origins -> per-class {0, 1} patches (mask_convert), NHWC ld 4,
+//                     merged by sw_merge_kernel like probabilities: the ground-truth branch;
+//   sw_mask_counts_kernel: two uint8 mask sets -> per-class pixel counts (both, prediction, ground truth), added to a buffer.
+// All restate integer / single-rounding arithmetic of the host functions get_patched_input, patch_merge and mask_convert and
+// are meant to match them bit for bit.  ABI: include/ssunet_hip.h.
 #include "common.h"
 
 namespace {
@@ -136,6 +139,102 @@ __global__ __launch_bounds__(256) void sw_merge_kernel(const float* __restrict__
   }
 }
 
+// The class a label pixel selects, as a bit set: its three bytes in memory order as one 24-bit value against the palette of
+// mask_convert -- class 0 (255, 255, 255), class 1 (255, 0, 0), class 2 (0, 0, 255).
+__device__ __forceinline__ void sw_label_hits(uint32_t px, int (&k)[3]) {
+  px &= 0xffffffu;
+  k[0] += px == 0xffffffu;
+  k[1] += px == 0x0000ffu;
+  k[2] += px == 0xff0000u;
+}
+
+// sw_gather_kernel's shape on a label image: one thread per output pixel, one 16-byte store each.  k = selected pixels of the
+// F x F source box; F = 1 stores k, F = 2 stores k >= 2: resize_u8 at 1/2 of a {0, 255} mask is (255 k + 2) >> 2 in
+// {0, 64, 128, 191, 255}, of which post_process_resized_mask keeps 128 and above.  Lanes C .. 3 are +0.0.
+template <int F>
+__global__ __launch_bounds__(256) void sw_gather_labels_kernel(const uint8_t* __restrict__ img, int H, int W, const int32_t* __restrict__ org,
+                                                               int out_size, int nb, int C, float* __restrict__ out) {
+  const int p = (int)(blockIdx.x / (unsigned)nb);
+  const int i = (int)(blockIdx.x % (unsigned)nb) * 256 + (int)threadIdx.x;
+  if (i >= out_size * out_size) return;
+  const int h1 = org[2 * p], w1 = org[2 * p + 1];
+  if (h1 < 0 || w1 < 0 || h1 > H - out_size * F || w1 > W - out_size * F) return;   // the entry point checked its host copy; never read outside
+  const int oy = i / out_size, ox = i - oy * out_size;
+  const long long total = (long long)H * W * 3;
+  int k[3] = {0, 0, 0};
+  if (F == 1) {
+    uint32_t lo, hi;
+    sw_bytes<3>(img, ((long long)(h1 + oy) * W + (w1 + ox)) * 3, total, lo, hi);
+    sw_label_hits(lo, k);
+  } else {
+    uint32_t lo0, hi0, lo1, hi1;
+    const long long b = ((long long)(h1 + 2 * oy) * W + (w1 + 2 * ox)) * 3;
+    sw_bytes<6>(img, b, total, lo0, hi0);
+    sw_bytes<6>(img, b + (long long)W * 3, total, lo1, hi1);
+    const uint64_t t = ((uint64_t)hi0 << 32) | lo0, u = ((uint64_t)hi1 << 32) | lo1;
+    sw_label_hits((uint32_t)t, k);
+    sw_label_hits((uint32_t)(t >> 24), k);
+    sw_label_hits((uint32_t)u, k);
+    sw_label_hits((uint32_t)(u >> 24), k);
+  }
+  f32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    if (c < C) o[c] = (F == 1 ? k[c] : (k[c] >= 2)) ? 1.f : 0.f;
+  *(f32x4*)(out + ((size_t)p * out_size * out_size + i) * 4) = o;
+}
+
+typedef uint32_t sw_u32x4 __attribute__((ext_vector_type(4)));
+
+// Per class (blockIdx.y) the pixels with pred > 127 and gt > 127, with pred > 127, with gt > 127 -- bit 7 of each byte, three
+// popcounts per 8 bytes -- added into counts[class][3].  A plane starts at any byte: the bytes before the prediction plane's
+// first 16-byte boundary and behind the last whole 16 are taken one by one, the rest 16 per thread and set; where the two
+// planes sit differently inside their 16-byte lines the whole plane goes byte by byte.  Blocks own contiguous chunks; sums are
+// reduced over the wave, then over the block's four waves in LDS, and three 64-bit integer atomics per block reach memory.
+__global__ __launch_bounds__(256) void sw_mask_counts_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restrict__ gt, long long HW,
+                                                             unsigned long long* __restrict__ counts) {
+  const int c = (int)blockIdx.y;
+  const uint8_t* p = pred + (size_t)c * HW;
+  const uint8_t* g = gt + (size_t)c * HW;
+  long long head = (long long)((16 - ((uintptr_t)p & 15)) & 15);
+  if (head > HW) head = HW;
+  const bool vec = (((uintptr_t)(g + head)) & 15) == 0;
+  const long long nv = vec ? (HW - head) / 16 : 0;           // 16-byte pieces, both planes aligned
+  const long long nbyte = HW - 16 * nv;                      // head and tail bytes (everything when not vec)
+  unsigned long long s[3] = {0, 0, 0};
+  SSG_CHUNK_LOOP(q, nv) {
+    const sw_u32x4 a = *(const sw_u32x4*)(p + head + 16 * q), b = *(const sw_u32x4*)(g + head + 16 * q);
+#pragma unroll
+    for (int e = 0; e < 4; e += 2) {
+      const uint64_t x = ((((uint64_t)a[e + 1] << 32) | a[e]) & 0x8080808080808080ull);
+      const uint64_t y = ((((uint64_t)b[e + 1] << 32) | b[e]) & 0x8080808080808080ull);
+      s[0] += (unsigned)__popcll(x & y);
+      s[1] += (unsigned)__popcll(x);
+      s[2] += (unsigned)__popcll(y);
+    }
+  }
+  SSG_CHUNK_LOOP(j, nbyte) {
+    const long long i = j < head ? j : j + 16 * nv;
+    const unsigned x = p[i] >> 7, y = g[i] >> 7;
+    s[0] += x & y;
+    s[1] += x;
+    s[2] += y;
+  }
+  __shared__ unsigned long long part[4][3];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s[e] += __shfl_xor(s[e], m, 64);
+  }
+  if ((threadIdx.x & 63) == 0)
+    for (int e = 0; e < 3; ++e) part[threadIdx.x >> 6][e] = s[e];
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const unsigned long long v = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+    if (v) atomicAdd(counts + 3 * c + threadIdx.x, v);
+  }
+}
+
 // host copy of the origin list: every patch inside the image
 int sw_check_origins(const int32_t* org_host, int P, int p_size, int H, int W, const char* who) {
   for (int p = 0; p < P; ++p) {
@@ -182,6 +281,41 @@ extern "C" int ssg_sw_merge_masks_f32_u8(const float* probs, int ld, int P, int 
     hipLaunchKernelGGL(sw_merge_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, probs, ld, P, C, S, org, weight, H, W, (int)nbx, out);
   else
     hipLaunchKernelGGL(sw_merge_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, probs, ld, P, C, S, org, weight, H, W, (int)nbx, out);
+  SSG_LAUNCH_CHECK();
+  return SSG_OK;
+}
+
+// mask_convert over every patch of a label image (aerial_image_segmentation_api.py:220-236,394-406)
+extern "C" int ssg_sw_gather_labels_u8_f32(const uint8_t* label, int H, int W, const int32_t* org, const int32_t* org_host, int P,
+                                           int p_size, int out_size, int C, float* out, void* stream) {
+  SSG_REQUIRE(label && org && org_host && out, SSG_EINVAL, "sw_gather_labels: null pointer");
+  SSG_REQUIRE(P > 0 && H > 0 && W > 0 && p_size > 0 && out_size > 0, SSG_EINVAL, "sw_gather_labels: bad sizes (P %d, image %d x %d, patch %d -> %d)", P, H, W, p_size, out_size);
+  SSG_REQUIRE(p_size == out_size || p_size == 2 * out_size, SSG_EINVAL, "sw_gather_labels: patch %d -> %d: only the factors 1 and 2 are built", p_size, out_size);
+  SSG_REQUIRE(C >= 1 && C <= 3, SSG_EINVAL, "sw_gather_labels: %d classes: the label palette has 3 colours", C);
+  if (int rc = sw_check_origins(org_host, P, p_size, H, W, "sw_gather_labels")) return rc;
+  SSG_REQUIRE((((uintptr_t)label) & 3) == 0 && ssg_aligned16(out) && (((uintptr_t)org) & 3) == 0, SSG_EALIGN, "sw_gather_labels: image 4-byte, output 16-byte aligned");
+  const long long nb = ssg_cdiv((long long)out_size * out_size, 256);
+  SSG_REQUIRE((long long)out_size * out_size < (1ll << 31) && nb * P < (1ll << 31), SSG_EINVAL, "sw_gather_labels: too large");
+  const dim3 grid((unsigned)(nb * P));
+  if (p_size == out_size)
+    hipLaunchKernelGGL(sw_gather_labels_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, label, H, W, org, out_size, (int)nb, C, out);
+  else
+    hipLaunchKernelGGL(sw_gather_labels_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, label, H, W, org, out_size, (int)nb, C, out);
+  SSG_LAUNCH_CHECK();
+  return SSG_OK;
+}
+
+// intersection / prediction / ground-truth pixel counts of the two mask sets (aerial_image_segmentation_api.py:220-236,394-406)
+extern "C" int ssg_sw_mask_counts_u8(const uint8_t* pred, const uint8_t* gt, int C, int64_t HW, uint64_t* counts, void* stream) {
+  SSG_REQUIRE(pred && gt && counts, SSG_EINVAL, "sw_mask_counts: null pointer");
+  SSG_REQUIRE(C >= 1 && C <= 65535 && HW > 0, SSG_EINVAL, "sw_mask_counts: bad sizes (%d classes of %lld pixels)", C, (long long)HW);
+  SSG_REQUIRE((((uintptr_t)counts) & 7) == 0, SSG_EALIGN, "sw_mask_counts: counts 8-byte aligned");
+  // 64 KiB of each set per block, at most 1024 blocks per class: the three atomics that end a block land on nine adjacent words,
+  // and at 2048^2 they, not the loads, were the time above the launch floor (768 blocks: +5.5 us, 192 blocks: +2.4 us)
+  long long gx = ssg_cdiv(HW, 65536);
+  if (gx > 1024) gx = 1024;
+  hipLaunchKernelGGL(sw_mask_counts_kernel, dim3((unsigned)gx, (unsigned)C), dim3(256), 0, (hipStream_t)stream, pred, gt, (long long)HW,
+                     (unsigned long long*)counts);
   SSG_LAUNCH_CHECK();
   return SSG_OK;
 }

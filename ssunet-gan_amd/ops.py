@@ -1965,6 +1965,52 @@ def sw_merge_masks(probs, origins, weights, p_size, img_h, img_w):
     return out
 
 
+def sw_gather_labels(label_u8, origins, p_size, out_size, classes=3):
+    """The ground-truth patches of the sliding-window pipeline from the label image on the device: for every origin (h1, w1)
+    and class c < classes, `mask_convert(label[h1:h1 + p_size, w1:w1 + p_size], c, out_size) / 255.0` of the host path
+    (p_size / out_size in {1, 2}).  `label_u8`: contiguous [H, W, 3] uint8, BGR.  Returns [P, classes, out_size, out_size]
+    fp32 NHWC (ld 4, pad lanes 0) holding 0.0 or 1.0 -- what `sw_merge_masks` takes."""
+    _lib.require_gpu(label_u8)
+    if label_u8.dtype != torch.uint8 or label_u8.dim() != 3 or label_u8.shape[2] != 3 or not label_u8.is_contiguous():
+        raise TypeError('sw_gather_labels: expected a contiguous [H, W, 3] uint8 label image, got %s %s' % (label_u8.dtype, tuple(label_u8.shape)))
+    _sw_factor(p_size, out_size, 'sw_gather_labels')
+    if not 1 <= classes <= 3:
+        raise ValueError('sw_gather_labels: %r classes: the label palette (mask_convert) has 3 colours' % (classes,))
+    host, devo = _sw_origins(origins, label_u8.device)
+    img_h, img_w = label_u8.shape[0], label_u8.shape[1]
+    _sw_inside(host, p_size, img_h, img_w, 'sw_gather_labels')
+    n = host.shape[0]
+    out = new_nhwc(n, classes, out_size, out_size, label_u8.device)
+    call('ssg_sw_gather_labels_u8_f32', ptr(label_u8), img_h, img_w, ptr(devo), ptr(host), n, p_size, out_size, classes,
+         ptr(out), stream_ptr())
+    return out
+
+
+def sw_mask_counts(pred, gt, out=None):
+    """Per class, the pixel counts (pred > 127 and gt > 127, pred > 127, gt > 127) of two uint8 mask sets [C, H, W] (or [C, HW])
+    on the device, as an int64 [C, 3] device tensor.  `out`: such a tensor to ADD the counts into (and return) -- an evaluation
+    loop accumulates over images without a host round trip."""
+    _lib.require_gpu(pred)
+    _lib.require_gpu(gt)
+    if pred.dtype != torch.uint8 or gt.dtype != torch.uint8 or pred.dim() < 2 or pred.shape != gt.shape:
+        raise TypeError('sw_mask_counts: expected two uint8 [C, H, W] mask sets of one shape, got %s %s and %s %s'
+                        % (pred.dtype, tuple(pred.shape), gt.dtype, tuple(gt.shape)))
+    if not (pred.is_contiguous() and gt.is_contiguous()):
+        raise TypeError('sw_mask_counts: the mask sets must be contiguous')
+    c = pred.shape[0]
+    hw = pred.numel() // c if c else 0
+    if c == 0 or hw == 0:
+        raise ValueError('sw_mask_counts: empty mask set %s' % (tuple(pred.shape),))
+    if out is None:
+        out = torch.zeros((c, 3), dtype=torch.int64, device=pred.device)
+    else:
+        _lib.require_gpu(out)
+        if out.dtype != torch.int64 or tuple(out.shape) != (c, 3) or not out.is_contiguous() or out.device != pred.device:
+            raise TypeError('sw_mask_counts: out must be a contiguous int64 [%d, 3] tensor on %s' % (c, pred.device))
+    call('ssg_sw_mask_counts_u8', ptr(pred), ptr(gt), c, hw, ptr(out), stream_ptr())
+    return out
+
+
 class _Mul(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
