@@ -145,6 +145,30 @@ int ssg_conv2d_bf16x1_f32(const ssg_conv_desc* d, const void* w_bf16x1, void* st
 int64_t ssg_pack_weights_bf16x1_bytes(int R, int Kp, int BN);
 int ssg_pack_weights_bf16x1(const float* w_packed, int R, int Kp, int BN, void* out, void* stream);
 
+/* Opt-in bf16x2 convolution (conv_halo_k32_x2.hip; ops.conv2d(..., precision='bf16x2')): the 3x3 stride-1 pad-1 conv (forward, and
+ * the input gradient as the same conv on dout with the transposed pack) with each operand split ONCE into two bf16 terms,
+ * x1 = bf16_rne(x), x2 = bf16_rne(x - x1), and three v_mfma_f32_16x16x32_bf16 per product in a fixed order, small terms first:
+ * x1 w2, x2 w1, x1 w1 (x2 w2 is dropped).  fp32 accumulation, epilogue and tensors.  An APPROXIMATION: |error| <= (3 * 2^-16 +
+ * 3 * 2^-32) * conv(|x|, |w|) from the dropped products, plus fp32 accumulation; half the matrix instructions of the fp32-class
+ * kernel.  Never selected by ssg_conv2d_f32 or ssg_conv2d_bf16x1_f32: the caller launches it by name.  The summation order does
+ * not depend on the grid.  Non-finite results are those of the fp32 kernels: an infinite (or bf16-overflowing, >= ~3.39e38)
+ * operand makes its second term a NaN, and a tile that holds a non-finite accumulator is recomputed in fp32.
+ * ssg_conv2d_bf16x2_ok: 0, or the pack format code (2128 / 2064 = 8 x 32-pixel x 128- / 64-channel tiles) the launch for `d`
+ * reads.  Legal: what ssg_conv2d_bf16x1_ok takes (the nine taps of a 3x3 window, kmode 0, unit strides, out_oy = out_ox = 0,
+ * C1 % 32 == 0, C2 % 32 == 0, Cout % 64 == 0, GW >= 17, 16-byte aligned pointers with ld % 4 == 0, inputs below 4 GiB, act none /
+ * ReLU / leaky ReLU, and bnpart, ws, parity_merge, in_scale, bwd_x unset).  d->w stays the fp32 packed matrix (the non-finite
+ * path reads it).
+ * ssg_pack_weights_bf16x2(d->w rows [R][Kp] in kmode 0, R, Kp, BN = that code): ssg_pack_weights_bf16x2_bytes bytes, layout
+ * [R/bn][Kp/32 steps = chunk32 * 9 + tap][2 planes][bn/16 fragments][64 lanes][16 B] (bn = BN - 2000; R % bn == 0, Kp % 288 == 0):
+ * plane 0 the rounded value, plane 1 the rounded residual; twice the bytes of the bf16x1 pack.
+ * ssg_conv2d_bf16x2_f32 validates on the host and returns a status before any launch.
+ * ssg_conv2d_bf16x2_kernel_id: 90 / 91 = conv_halo_k32_x2_kernel<128> / <64> (profiling labels), SSG_EINVAL where refused. */
+int ssg_conv2d_bf16x2_ok(const ssg_conv_desc* d);
+int ssg_conv2d_bf16x2_kernel_id(const ssg_conv_desc* d);
+int ssg_conv2d_bf16x2_f32(const ssg_conv_desc* d, const void* w_bf16x2, void* stream);
+int64_t ssg_pack_weights_bf16x2_bytes(int R, int Kp, int BN);
+int ssg_pack_weights_bf16x2(const float* w_packed, int R, int Kp, int BN, void* out, void* stream);
+
 /* Opt-in bf16x1 kernels for the 3x3 STRIDE-2 pad-1 conv (models_seg_gan.py:37-39, the discriminator's s2 blocks) and its input
  * gradient (conv_s2_k32_x1.hip; ops.conv2d(..., precision='bf16x1')): the contract of ssg_conv2d_bf16x1_f32 -- operands rounded once
  * to bf16, fp32 accumulation, fp32 tensors, non-finite results those of the fp32 kernels -- with one input (C2 = 0) and no res.
@@ -264,6 +288,20 @@ int ssg_conv2d_wgrad_bf16x1_ok(const ssg_wgrad_desc* d);
 int64_t ssg_conv2d_wgrad_bf16x1_workspace_bytes(const ssg_wgrad_desc* d);
 int ssg_conv2d_wgrad_bf16x1_f32(const ssg_wgrad_desc* d, void* stream);
 int ssg_conv2d_wgrad_bf16x1_kernel_id(const ssg_wgrad_desc* d);
+
+/* Opt-in bf16x2 weight gradient (conv_wgrad_k32_x2.hip; precision 'bf16x2'): the contract, legal shapes, workspace and ordered
+ * split-K reduction of the bf16x1 group above, with both operands (the x window and dout) split once into two bf16 terms and three
+ * MFMAs per product, small terms first: x1 d2, x2 d1, x1 d1.  An APPROXIMATION: |error| <= (3 * 2^-16 + 3 * 2^-32) * sum |in| |dout|
+ * plus the fp32 accumulation error; neither ssg_conv2d_wgrad_f32 nor ssg_conv2d_wgrad_bf16x1_f32 routes here.  A workgroup that
+ * holds a non-finite accumulator (every one that read an infinite or bf16-overflowing operand) recomputes its tile in fp32.
+ * ssg_conv2d_wgrad_bf16x2_ok: 1 where the launch takes `d` (the predicate of ssg_conv2d_wgrad_bf16x1_ok), else 0.
+ * ssg_conv2d_wgrad_bf16x2_workspace_bytes: bytes of d->ws for the split-K slabs (0 where refused).
+ * ssg_conv2d_wgrad_bf16x2_f32 validates on the host and returns a status before any launch; d->flags is ignored.
+ * ssg_conv2d_wgrad_bf16x2_kernel_id: 92 = wgrad_k32_x2_kernel (profiling label), SSG_EINVAL where refused. */
+int ssg_conv2d_wgrad_bf16x2_ok(const ssg_wgrad_desc* d);
+int64_t ssg_conv2d_wgrad_bf16x2_workspace_bytes(const ssg_wgrad_desc* d);
+int ssg_conv2d_wgrad_bf16x2_f32(const ssg_wgrad_desc* d, void* stream);
+int ssg_conv2d_wgrad_bf16x2_kernel_id(const ssg_wgrad_desc* d);
 
 /* Opt-in bf16x1 weight gradient of the 3x3 STRIDE-2 pad-1 conv (conv_wgrad_s2_k32_x1.hip; precision 'bf16x1' with wgrad_s2 'bf16x1'):
  * the contract, rounding, error bound and non-finite guard of the group above, dw[ky][kx][ci][co] = sum in[n, 2oy + ky - 1,

@@ -95,6 +95,11 @@ SIGNATURES = {
     'ssg_conv2d_bf16x1_f32': [C.POINTER(ConvDesc), _P, _P],
     'ssg_pack_weights_bf16x1_bytes': [_I, _I, _I],
     'ssg_pack_weights_bf16x1': [_P, _I, _I, _I, _P, _P],
+    'ssg_conv2d_bf16x2_ok': [C.POINTER(ConvDesc)],
+    'ssg_conv2d_bf16x2_kernel_id': [C.POINTER(ConvDesc)],
+    'ssg_conv2d_bf16x2_f32': [C.POINTER(ConvDesc), _P, _P],
+    'ssg_pack_weights_bf16x2_bytes': [_I, _I, _I],
+    'ssg_pack_weights_bf16x2': [_P, _I, _I, _I, _P, _P],
     'ssg_conv2d_bf16x1_s2_ok': [C.POINTER(ConvDesc)],
     'ssg_conv2d_bf16x1_s2_kernel_id': [C.POINTER(ConvDesc)],
     'ssg_conv2d_bf16x1_s2_f32': [C.POINTER(ConvDesc), _P, _P],
@@ -107,6 +112,10 @@ SIGNATURES = {
     'ssg_conv2d_wgrad_bf16x1_kernel_id': [C.POINTER(WgradDesc)],
     'ssg_conv2d_wgrad_bf16x1_workspace_bytes': [C.POINTER(WgradDesc)],
     'ssg_conv2d_wgrad_bf16x1_f32': [C.POINTER(WgradDesc), _P],
+    'ssg_conv2d_wgrad_bf16x2_ok': [C.POINTER(WgradDesc)],
+    'ssg_conv2d_wgrad_bf16x2_kernel_id': [C.POINTER(WgradDesc)],
+    'ssg_conv2d_wgrad_bf16x2_workspace_bytes': [C.POINTER(WgradDesc)],
+    'ssg_conv2d_wgrad_bf16x2_f32': [C.POINTER(WgradDesc), _P],
     'ssg_conv2d_wgrad_bf16x1_s2_ok': [C.POINTER(WgradDesc)],
     'ssg_conv2d_wgrad_bf16x1_s2_kernel_id': [C.POINTER(WgradDesc)],
     'ssg_conv2d_wgrad_bf16x1_s2_workspace_bytes': [C.POINTER(WgradDesc)],
@@ -212,9 +221,11 @@ _RESTYPES = {
     'ssg_conv2d_wgrad_workspace_bytes': C.c_int64,
     'ssg_conv2d_wgrad_bf16x1_workspace_bytes': C.c_int64,
     'ssg_conv2d_wgrad_bf16x1_s2_workspace_bytes': C.c_int64,
+    'ssg_conv2d_wgrad_bf16x2_workspace_bytes': C.c_int64,
     'ssg_conv2d_workspace_bytes': C.c_int64,
     'ssg_pack_weights_split_bytes': C.c_int64,
     'ssg_pack_weights_bf16x1_bytes': C.c_int64,
+    'ssg_pack_weights_bf16x2_bytes': C.c_int64,
     'ssg_pack_weights_bf16x1_taps_bytes': C.c_int64,
     'ssg_bn_workspace_bytes': C.c_int64,
     'ssg_se_gate_workspace_floats': C.c_int64,
@@ -227,7 +238,7 @@ _RESTYPES = {
     'ssg_conv2d_thin_bf16_wgrad_workspace_bytes': C.c_int64,
     'ssg_bn_stats_from_partials_workspace_bytes': C.c_int64,
 }
-_NO_STATUS = set(_RESTYPES) | {'ssg_abi_version', 'ssg_conv2d_split_bn', 'ssg_conv2d_in_affine_ok', 'ssg_conv2d_wgrad_in_affine_ok', 'ssg_conv2d_bwd_stats_ok', 'ssg_conv2d_kernel_id', 'ssg_conv2d_bnpart_rows', 'ssg_conv2d_bf16x1_ok', 'ssg_conv2d_bf16x1_kernel_id', 'ssg_conv2d_bf16x1_s2_ok', 'ssg_conv2d_bf16x1_s2_kernel_id', 'ssg_conv2d_bf16x1_cls_ok', 'ssg_conv2d_bf16x1_cls_kernel_id', 'ssg_conv2d_wgrad_bf16x1_ok', 'ssg_conv2d_wgrad_bf16x1_kernel_id', 'ssg_conv2d_wgrad_bf16x1_s2_ok', 'ssg_conv2d_wgrad_bf16x1_s2_kernel_id', 'ssg_conv2d_wgrad_kernel_id', 'ssg_dwconv2d_kernel_id',
+_NO_STATUS = set(_RESTYPES) | {'ssg_abi_version', 'ssg_conv2d_split_bn', 'ssg_conv2d_in_affine_ok', 'ssg_conv2d_wgrad_in_affine_ok', 'ssg_conv2d_bwd_stats_ok', 'ssg_conv2d_kernel_id', 'ssg_conv2d_bnpart_rows', 'ssg_conv2d_bf16x1_ok', 'ssg_conv2d_bf16x1_kernel_id', 'ssg_conv2d_bf16x2_ok', 'ssg_conv2d_bf16x2_kernel_id', 'ssg_conv2d_wgrad_bf16x2_ok', 'ssg_conv2d_wgrad_bf16x2_kernel_id', 'ssg_conv2d_bf16x1_s2_ok', 'ssg_conv2d_bf16x1_s2_kernel_id', 'ssg_conv2d_bf16x1_cls_ok', 'ssg_conv2d_bf16x1_cls_kernel_id', 'ssg_conv2d_wgrad_bf16x1_ok', 'ssg_conv2d_wgrad_bf16x1_kernel_id', 'ssg_conv2d_wgrad_bf16x1_s2_ok', 'ssg_conv2d_wgrad_bf16x1_s2_kernel_id', 'ssg_conv2d_wgrad_kernel_id', 'ssg_dwconv2d_kernel_id',
                                 'ssg_spade_conv_modulate_ok', 'ssg_se_gate_ok'}
 
 ABI_VERSION = 10         # ssg_abi_version() of the library this ctypes table (ConvDesc layout, SIGNATURES) was written against

@@ -65,7 +65,7 @@ def _cached_operands(model):
     (`blocks._spade_cat`) caches of `model` hold right now."""
     held = []
     for t in list(model.parameters()) + list(model.buffers()):
-        for name in ('_ssg_pack', '_ssg_pack_bf16', '_ssg_pack_bf16x1'):
+        for name in ('_ssg_pack', '_ssg_pack_bf16', '_ssg_pack_bf16x1', '_ssg_pack_bf16x2'):
             c = t.__dict__.get(name)
             if c is not None:
                 held += list(c[1].values())
@@ -77,7 +77,7 @@ def _cached_operands(model):
         if c is not None:
             held += list(c[1])
             for t in c[1]:                       # the folded weights are themselves packed per use
-                for name in ('_ssg_pack', '_ssg_pack_bf16x1'):
+                for name in ('_ssg_pack', '_ssg_pack_bf16x1', '_ssg_pack_bf16x2'):
                     p = t.__dict__.get(name)
                     if p is not None:
                         held += list(p[1].values())
@@ -128,7 +128,9 @@ def infer_patches(model, img_patch_set, batch_size=16, graph=False, precision='f
     speed: the 3x3 stride-1 convs of the model's eval-mode BasicBlocks whose shape the one-term kernel takes (32-channel multiples
     in, 64 out, at least 17 pixels wide: not the stem's 3-channel conv, not the 16x16 levels) round x and the BN-folded weights
     once to bf16 and accumulate in fp32 (`ops.conv2d_bf16x1`).  The 1x1 shortcuts, stride-2 convs, SPADE, pooling and resampling
-    layers and every tensor in memory stay fp32.  Any other string raises ValueError."""
+    layers and every tensor in memory stay fp32.  'bf16x2': the same convs with each operand split into two bf16 terms and three
+    products kept (`ops.conv2d(..., precision='bf16x2')`): |error| <= (3 * 2^-16 + 3 * 2^-32) conv(|x|, |w|) per conv, half the matrix
+    instructions of the default.  Any other string raises ValueError."""
     x = torch.as_tensor(img_patch_set, dtype=torch.float32)
     model.eval()
     outs = []

@@ -65,7 +65,13 @@ class BasicBlock(nn.Module):
         # ops.infer_precision('bf16x1') (an opt-in approximation, eval mode only): the two 3x3 convs run on the one-term bf16 kernel
         # where it takes the shape (unit stride, 32-channel multiples in, 64 out, >= 17 pixels wide) and stay on the fp32-class
         # kernel elsewhere; the folded weights are what it packs.  The 1x1 shortcut is never touched.
-        x1 = ops.infer_precision_mode() == 'bf16x1'
+        # infer_precision('bf16x2'): the same two convs ask the two-term kernel through conv2d(precision=), which declines per launch.
+        mode = ops.infer_precision_mode()
+        x1 = mode == 'bf16x1'
+        if mode == 'bf16x2':
+            y = ops.conv2d(x, w1, b1, s, 1, act=ACT_RELU, x2=x2, precision=mode)
+            r = ops.conv2d(x, sc.weight, None, s, 0, x2=x2) if sc is not None else x
+            return ops.conv2d(y, w2, b2, 1, 1, act=ACT_RELU, res=r, precision=mode)
         if x1 and s == 1 and ops.conv2d_bf16x1_ok(x, w1, x2=x2):
             y = ops.conv2d_bf16x1(x, w1, b1, act=ACT_RELU, x2=x2)
         else:

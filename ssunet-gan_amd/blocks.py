@@ -21,7 +21,14 @@ from .ops import (_act_bwd, _bn_bwd_impl, _bn_fwd_impl, _channel_sum, _conv_dgra
 # `x1m` is the mode a node's FORWARD read (and its stride is 1): the node then passes precision='bf16x1' to its two 3x3 convs in
 # all three directions.  Each launch runs on the one-term bf16 kernel only where its own predicate holds
 # (ssg_conv2d_bf16x1_ok / ssg_conv2d_wgrad_bf16x1_ok: 64-channel multiples, >= 17 pixels wide); a refused launch runs on the
-# fp32-class kernel it runs on today.  The 1x1 shortcut always passes 'fp32'.
+# fp32-class kernel it runs on today.  The 1x1 shortcut always passes 'fp32'.  train_precision('bf16x2') is handled alike: `x1m` is
+# then 'bf16x2' and the launches ask the two-term kernels (ssg_conv2d_bf16x2_ok / ssg_conv2d_wgrad_bf16x2_ok, the same shapes).
+def _x_mode(stride):
+    """'bf16x1' / 'bf16x2' where train_precision names one and the block's stride is 1, else False."""
+    mode = ops.train_precision_mode()
+    return mode if mode != 'fp32' and stride == 1 else False
+
+
 class _BasicBlockFn(torch.autograd.Function):
     """relu(bn1(conv3x3(x))) -> bn2(conv3x3(.)) -> (+ conv1x1(x) | + x) -> relu, x = cat(x1, x2)."""
 
@@ -29,8 +36,8 @@ class _BasicBlockFn(torch.autograd.Function):
     def forward(ctx, x1, x2, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, wsc, eps1, mom1, eps2, mom2, stride, var_mode, group):
         x1 = to_nhwc(x1)
         x2 = to_nhwc(x2) if x2 is not None else None
-        ctx.x1m = x1m = ops.train_precision_mode() == 'bf16x1' and stride == 1
-        p3 = 'bf16x1' if x1m else 'fp32'
+        ctx.x1m = x1m = _x_mode(stride)
+        p3 = x1m or 'fp32'
         # batch-norm statistics ride the producing conv's epilogue where its kernel has one (part = None otherwise: the bf16x1
         # launcher has none, so behind a routed conv the batch norm runs its own statistics pass)
         c1, part1 = _conv_fwd_impl(x1, x2, w1, None, stride, 1, ACT_NONE, 0.0, want_bn=True, precision=p3)
@@ -68,7 +75,7 @@ class _BasicBlockFn(torch.autograd.Function):
         x1, x2, c1, y1, c2, out, w1, g1, w2, g2, wsc, st1, st2 = ctx.saved_tensors
         stride, group, cnt1, cnt2 = ctx.cfg
         x1m = ctx.x1m                                    # the forward's train_precision mode, whatever is set now
-        p3 = 'bf16x1' if x1m else 'fp32'
+        p3 = x1m or 'fp32'
         dout = to_nhwc(dout)
         n, ca, h, w = x1.shape
         cb = x2.shape[1] if x2 is not None else 0
@@ -147,8 +154,8 @@ class _FrozenBasicBlockFn(torch.autograd.Function):
         x2 = to_nhwc(x2) if x2 is not None else None
         # train_precision('bf16x1'): the folded convs with their bias / ReLU / residual epilogues on the bf16x1 kernel, as the eval
         # path under infer_precision; only a forward that records a graph reads the mode
-        x1m = record and any(ctx.needs_input_grad) and ops.train_precision_mode() == 'bf16x1' and stride == 1
-        p3 = 'bf16x1' if x1m else 'fp32'
+        x1m = record and any(ctx.needs_input_grad) and _x_mode(stride)
+        p3 = x1m or 'fp32'
         y1 = _conv_fwd_impl(x1, x2, wf1, bf1, stride, 1, ACT_RELU, 0.0, precision=p3)
         if wsc is not None:
             r = _conv_fwd_impl(x1, x2, wsc, None, stride, 0, ACT_NONE, 0.0)
@@ -168,7 +175,7 @@ class _FrozenBasicBlockFn(torch.autograd.Function):
     def backward(ctx, dout):
         x1, x2, y1, out, w1, w2, wsc, wf1, wf2, s1, m1, is1, s2, m2, is2 = ctx.saved_tensors
         stride = ctx.stride
-        p3 = 'bf16x1' if ctx.x1m else 'fp32'             # the forward's train_precision mode, whatever is set now
+        p3 = ctx.x1m or 'fp32'                           # the forward's train_precision mode, whatever is set now
         dout = to_nhwc(dout)
         n, ca, h, w = x1.shape
         cb = x2.shape[1] if x2 is not None else 0

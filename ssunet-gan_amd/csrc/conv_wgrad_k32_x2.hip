@@ -1,0 +1,361 @@
+// Weight gradient of 3x3 stride-1 pad-1 convolutions, TWO-TERM form on v_mfma_f32_16x16x32_bf16 (opt-in precision 'bf16x2').  The
+// contract of wgrad_k32_x1_kernel (conv_wgrad_k32_x1.hip), whose body this is: dW[tap][ci][co] = sum over pixels of
+// x[p + tap][ci] * dy[p][co], fp32 tensors in HBM, one or two input pointers (concat), split-K slabs [split][tap * Cin + ci][Cout]
+// reduced in order by wgrad_reduce_kernel, OIHW output.  The difference: both operands (the x window and dy) are split ONCE into
+// two bf16 terms on the way into LDS (split2_4 in mfma_split.h: v1 = bf16_rne(v), v2 = bf16_rne(v - v1)), two planes per slot, and
+// a product is three MFMAs in a fixed order, small terms first: x1 * d2, x2 * d1, x1 * d1 (x2 * d2 is dropped):
+// |x d - kept| <= (3 * 2^-16 + 3 * 2^-32) |x d|.  Nothing routes here unless the caller asks (ssg_conv2d_wgrad_bf16x2_f32).
+// Kept from the one-term kernel: the bf16 plane [pixel][64 channels] in 128-byte rows with the chunk XOR keyed by pixel bits 1 and
+// 3, fragments by ds_read_b64_tr_b16, a K-step = 32 pixels of one image row, steps walking DOWN a 32-pixel column strip with the x
+// window rolling through 8 LDS row slots (dy through 4), a barrier interval of TWO image rows whose successors are loaded in two
+// halves, dy as the A operand so that a lane stores 4 consecutive output channels, the tile 9 taps x 64 input channels x 128
+// output channels where Cout % 128 == 0 (NJ = 4) and 9 x 64 x 64 (NJ = 2) elsewhere, the slab plan and the ordered reduction.
+// The three terms of an x row run as three sweeps over its 3 * NJ accumulators, so a dependent MFMA is 3 * NJ issues behind.
+// LDS: x 2 planes x 8 slots x 36 pixels x 128 B = 72 KB, dy 2 planes x 4 slots x (NJ / 2) x 32 x 128 B = 32 / 64 KB: 104 / 136 KB,
+// one 512-thread workgroup per CU.  Registers: 36 / 18 accumulators x 4, 2 x (NJ + 3) fragments x 4, one row of staging values.
+// The summation order is fixed by (slab, K-step, term) and the slabs are reduced in order: it does not depend on the grid
+// beyond the slab plan, which is a function of the shape alone.
+// Legal shapes (ssg_conv2d_wgrad_bf16x2_ok): those of ssg_conv2d_wgrad_bf16x2_ok.
+// Non-finite operands (conv_slow.h): REQUIRED here -- an infinite v1 makes v - v1 a NaN, so every workgroup that reads an infinite
+// or bf16-overflowing operand holds a non-finite accumulator and recomputes its tile from the fp32 operands.
+#include "common.h"
+#include "lds_dma.h"
+#include "conv_wgrad_args.h"
+#include "mfma_split.h"
+#include "conv_slow.h"
+
+namespace {
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+
+constexpr int KP = 32;                     // pixels per K-step
+constexpr int WPX = 36;                    // pixel rows per x slot (34 used: window columns gx0 - 1 .. gx0 + 32)
+constexpr int XSLOT = WPX * 128;           // bytes
+constexpr int XSLOTS = 8;
+constexpr int XIMG = XSLOTS * XSLOT;
+constexpr int DHALF = KP * 128;            // one dy row, 64 output channels
+constexpr int DSLOTS = 4;
+constexpr int CB = 64;
+constexpr int MAX_ROWS = 128;              // longest accumulation chain of a slab, in K-steps (4096 pixels: wgrad_k32's)
+constexpr int MIN_ROWS = 8;
+constexpr int x2_lds_bytes(int NJ) { return 2 * (XIMG + DSLOTS * (NJ / 2) * DHALF); }      // two planes of each image
+
+// 16-byte chunk c (0..7) of pixel row p sits at chunk position c ^ sw(p)
+__device__ __forceinline__ int sw(int p) { return ((((p >> 1) & 1) | (((p >> 3) & 1) << 1)) << 1); }
+
+template <int NJ>
+__global__ __launch_bounds__(512, 1) void wgrad_k32_x2_kernel(const WgArgs a) {
+  constexpr int NH = NJ / 2;                             // 64-channel halves of a dy row
+  constexpr int BN = 32 * NJ;
+  constexpr int DSLOT = NH * DHALF;
+  static_assert(NJ == 2 || NJ == 4, "64 or 128 output channels per workgroup");
+  static_assert(4 * 512 * 4 <= x2_lds_bytes(NJ), "the slow path's scratch (one accumulator per thread) fits the LDS allocation");
+  extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
+  unsigned char* const ximg = lds;
+  constexpr int DIMG = DSLOTS * DSLOT;
+  unsigned char* const dimg = lds + 2 * XIMG;            // plane 1 of x at ximg + XIMG, of dy at dimg + DIMG
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;               // 16-channel block of the 64, group of NJ output-channel fragments
+  const int l15 = lane & 15, g = lane >> 4;
+  const int c0 = blockIdx.x * CB, n0 = blockIdx.y * BN;
+  const int Cin = a.C1 + a.C2;
+  const int XB = (a.GW + KP - 1) / KP;
+
+  // ---- this workgroup's range of K-steps, S = strip * GH + gy (strip = image * XB + column strip)
+  const long long total = (long long)a.N * XB * a.GH;
+  long long S0 = (long long)blockIdx.z * a.steps_per_split, S1 = S0 + a.steps_per_split;
+  if (S1 > total) S1 = total;
+
+  const unsigned OOB = 0xffffffffu;
+  const bool first = c0 < a.C1;
+  const float* xsrc = first ? a.in1 : a.in2;
+  const int xld = first ? a.ld1 : a.ld2;
+  const int xc0 = first ? c0 : c0 - a.C1;
+  const unsigned npix = (unsigned)a.N * (unsigned)a.H * (unsigned)a.W;
+  const auto x_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xsrc), 0, (int)(npix * (unsigned)xld * 4u), 0x00020000);
+  const auto d_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dout), 0, (int)((unsigned)a.N * (unsigned)a.GH * (unsigned)a.GW * (unsigned)a.ldd * 4u), 0x00020000);
+
+  // ---- staging items, 16-byte pieces in lane order (wgrad_k32_kernel's): piece t of a new x row = (window pixel t >> 4, quarter
+  // t & 15) for every thread, pieces 512..543 (window pixels 32, 33) once more for threads 0..31; piece t of each 64-channel half
+  // of a dy row for every thread.  Out-of-image pieces read zeros through the descriptor's range check.
+  const int s_px = tid >> 4, s_q = tid & 15;
+  const bool has_x2 = tid < 32;
+  const int x_dst = s_px * 128 + (((s_q >> 1) ^ sw(s_px)) << 4) + (s_q & 1) * 8;
+  const int x_dst2 = (32 + s_px) * 128 + (((s_q >> 1) ^ sw(32 + s_px)) << 4) + (s_q & 1) * 8;      // threads 0..31: s_px = 0, 1
+  const int d_dst = x_dst;                               // same (pixel, quarter) position in a dy half
+
+  struct RawX { u32x4 a, b; };
+  struct RawD { u32x4 h[NH]; };
+  auto x_inside = [&](int row, int gx0, int px) -> bool {        // is window pixel px of row `row` inside the image
+    return (unsigned)row < (unsigned)a.H && (unsigned)(gx0 - 1 + px) < (unsigned)a.W;
+  };
+  auto load_x = [&](int n, int row, int gx0) -> RawX {   // window row `row` (may be -1 or >= H: zeros), columns gx0 - 1 .. gx0 + 32
+    const unsigned rowbase = (unsigned)((n * a.H + row) * a.W + gx0 - 1);
+    const unsigned cho = (unsigned)(xc0 + 4 * s_q) * 4u;
+    const unsigned vo = x_inside(row, gx0, s_px) ? (rowbase + (unsigned)s_px) * (unsigned)xld * 4u + cho : OOB;
+    const unsigned vo2 = (has_x2 && x_inside(row, gx0, 32 + s_px)) ? (rowbase + 32u + (unsigned)s_px) * (unsigned)xld * 4u + cho : OOB;
+    RawX r;
+    r.a = __builtin_amdgcn_raw_buffer_load_b128(x_rs, vo, 0, 0);
+    r.b = __builtin_amdgcn_raw_buffer_load_b128(x_rs, vo2, 0, 0);
+    return r;
+  };
+  auto load_d = [&](int n, int gy, int gx0) -> RawD {    // row gy (may be >= GH: zeros, never multiplied)
+    const int gx = gx0 + s_px;
+    const bool ok = gy < a.GH && gx < a.GW;
+    RawD r;
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const unsigned vo = ok ? (unsigned)((n * a.GH + gy) * a.GW + gx) * (unsigned)a.ldd * 4u + (unsigned)(n0 + 64 * h + 4 * s_q) * 4u : OOB;
+      r.h[h] = __builtin_amdgcn_raw_buffer_load_b128(d_rs, vo, 0, 0);
+    }
+    return r;
+  };
+  auto put = [&](unsigned char* dst, int plane, u32x4 raw) {      // both terms, `plane` bytes apart
+    bf16x4 p1, p2;
+    split2_4(__builtin_bit_cast(f32x4, raw), p1, p2);    // NaN stays NaN; |v| >= 2^128 - 2^119: p1 = inf, p2 = NaN
+    *(bf16x4*)dst = p1;
+    *(bf16x4*)(dst + plane) = p2;
+  };
+  auto store_x = [&](const RawX& r, int slot) {
+    put(ximg + slot * XSLOT + x_dst, XIMG, r.a);
+    if (has_x2) put(ximg + slot * XSLOT + x_dst2, XIMG, r.b);
+  };
+  auto store_d = [&](const RawD& r, int slot) {
+#pragma unroll
+    for (int h = 0; h < NH; ++h) put(dimg + slot * DSLOT + h * DHALF + d_dst, DIMG, r.h[h]);
+  };
+
+  // ---- transposed-read addresses.  Operand k-group g covers pixels 8g .. 8g+7 of the step; lane 4q+pp of the group supplies pixel
+  // row q (t adds 4), channels 4pp .. 4pp+3 of the 16-channel block
+  const int q4 = l15 >> 2, pp = l15 & 3;
+  int xoff[3][2], doff[NJ][2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const int p = dx + 8 * g + q4 + 4 * t;             // window pixel: step pixel + 1 + (dx - 1)
+      xoff[dx][t] = p * 128 + ((((2 * wm + (pp >> 1)) ^ sw(p))) << 4) + (pp & 1) * 8;
+    }
+    const int p = 8 * g + q4 + 4 * t;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int blk = NJ * wn + j;                       // 16-channel block of the BN output channels: half blk >> 2, block blk & 3 of it
+      doff[j][t] = (blk >> 2) * DHALF + p * 128 + ((((2 * (blk & 3) + (pp >> 1)) ^ sw(p))) << 4) + (pp & 1) * 8;
+    }
+  }
+
+  // One accumulator sums a whole slab: the planner keeps a slab at <= MAX_ROWS K-steps (4096 pixels), as for wgrad_k32_kernel.
+  f32x4 acc[9][NJ];
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  auto frag = [&](const unsigned char* base, int o0, int o1) -> bf16x8 {
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + o0));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + o1));
+    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_bit_cast(bf16x8, v);
+  };
+
+  long long S = S0;
+  while (S < S1) {
+    // ---- segment: rows [ga, gb) of one column strip
+    const int strip = (int)(S / a.GH), ga = (int)(S - (long long)strip * a.GH);
+    long long Se = (long long)(strip + 1) * a.GH;
+    if (Se > S1) Se = S1;
+    const int gb = ga + (int)(Se - S);
+    const int n = strip / XB, gx0 = (strip - n * XB) * KP;
+
+    // prologue: x rows ga-1 .. ga+2 and dy rows ga, ga+1.  x row r sits in slot (r + 1) & 7, dy row r in slot r & 3.
+    wait_lds_reads();
+    __builtin_amdgcn_s_barrier();                        // the previous segment's last reads are done
+    asm volatile("" ::: "memory");
+    {                                                    // two batches: four rows in flight at once spilled registers
+      const RawX r0 = load_x(n, ga - 1, gx0), r1 = load_x(n, ga, gx0);
+      const RawD d0 = load_d(n, ga, gx0);
+      store_x(r0, (ga + 0) & 7); store_x(r1, (ga + 1) & 7); store_d(d0, ga & 3);
+    }
+    {
+      const RawX r2 = load_x(n, ga + 1, gx0), r3 = load_x(n, ga + 2, gx0);
+      const RawD d1 = load_d(n, ga + 1, gx0);
+      store_x(r2, (ga + 2) & 7); store_x(r3, (ga + 3) & 7); store_d(d1, (ga + 1) & 3);
+    }
+
+    for (int gy = ga; gy < gb; gy += 2) {
+      wait_lds_reads();
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      const bool more = gy + 2 < gb;
+      // the next interval's rows (x gy+3, gy+4 and dy gy+2, gy+3) come in two halves, each in flight behind one row of MFMAs and
+      // written into slots no wave reads in this interval: one row of staging registers instead of two
+      RawX nx; RawD nd;
+      if (more) { nx = load_x(n, gy + 3, gx0); nd = load_d(n, gy + 2, gx0); }
+      const int nrows = gy + 1 < gb ? 2 : 1;             // a segment with an odd number of rows ends on a one-row interval
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr) {
+        if (rr < nrows) {
+          const int row = gy + rr;
+          if (rr == 0) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1);      // a wave's priority falls as it advances through an interval
+          const unsigned char* db = dimg + (row & 3) * DSLOT;
+          bf16x8 df[2][NJ];                              // [plane]
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) df[h][j] = frag(db + h * DIMG, doff[j][0], doff[j][1]);
+#pragma unroll
+          for (int dyi = 0; dyi < 3; ++dyi) {
+            const unsigned char* xb = ximg + ((row + dyi) & 7) * XSLOT;     // x row (row - 1 + dyi) -> slot (x row + 1) & 7
+            bf16x8 xf[2][3];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+              for (int dx = 0; dx < 3; ++dx) xf[h][dx] = frag(xb + h * XIMG, xoff[dx][0], xoff[dx][1]);
+            // A = dy (rows = output channels), B = x (columns = input channels); small terms first: x1 d2, x2 d1, x1 d1
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+              const int hd = t == 0 ? 1 : 0, hx = t == 1 ? 1 : 0;
+#pragma unroll
+              for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+                for (int j = 0; j < NJ; ++j)
+                  acc[dyi * 3 + dx][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df[hd][j], xf[hx][dx], acc[dyi * 3 + dx][j], 0, 0, 0);
+            }
+          }
+        }
+        if (more) {
+          __builtin_amdgcn_sched_barrier(0);
+          store_x(nx, (gy + 4 + rr) & 7);
+          store_d(nd, (gy + 2 + rr) & 3);
+          if (rr == 0) { nx = load_x(n, gy + 4, gx0); nd = load_d(n, gy + 3, gx0); }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+    }
+    S = Se;
+  }
+
+  wait_lds_reads();
+  {                                                      // non-finite operands: conv_slow.h
+    bool bad = false;
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bad |= ssg_nonfinite(acc[t][j][r]);
+    if (ssg_any_nonfinite(bad)) {
+      const WgArgs& as = *ssg_reload_args<WgArgs>();
+#pragma unroll
+      for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          ssg_slow_refill4(acc[t][j], (float*)lds + tid, 512, [&](int r) {
+            return ssg_wgrad_slow_value_strips<false>(as, t, c0 + wm * 16 + l15, n0 + (NJ * wn + j) * 16 + 4 * g + r, S0, S1, KP);
+          });
+    }
+  }
+
+  // ---- slab [split][row = tap * Cin + ci][Cout]: acc[tap][j][r] = (ci = c0 + wm*16 + l15, co = n0 + (NJ*wn + j)*16 + 4g + r)
+  float* slab = a.ws + (size_t)blockIdx.z * a.M * a.Cout;
+  const int ci = c0 + wm * 16 + l15;
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+      *(f32x4*)(slab + ((size_t)t * Cin + ci) * a.Cout + n0 + (NJ * wn + j) * 16 + 4 * g) = acc[t][j];
+}
+
+struct X2Plan { int nj, mt, nt, splits, steps_per_split; };
+
+// The shape test alone (no pointers): what ssg_conv2d_wgrad_bf16x2_ok answers.
+bool x2_shape_ok(const ssg_wgrad_desc* d) {
+  if (!d || d->in_scale || d->in_shift) return false;
+  if (d->ntaps != 9 || d->KH != 3 || d->KW != 3 || d->in_sy != 1 || d->in_sx != 1) return false;
+  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->GH != d->H || d->GW != d->W) return false;
+  for (int t = 0; t < 9; ++t)
+    if (d->dy[t] != t / 3 - 1 || d->dx[t] != t % 3 - 1 || d->ky[t] != t / 3 || d->kx[t] != t % 3) return false;
+  if (d->C1 <= 0 || d->C1 % 64 || d->C2 < 0 || d->C2 % 64 || d->Cout <= 0 || d->Cout % 64 || d->GW < 17) return false;
+  if (d->Cin_real != d->C1 + d->C2) return false;
+  if ((d->ld1 & 3) || d->ld1 < d->C1 || (d->C2 && ((d->ld2 & 3) || d->ld2 < d->C2)) || (d->ldd & 3) || d->ldd < d->Cout) return false;
+  const unsigned long long xb = (unsigned long long)d->N * d->H * d->W * (unsigned long long)(d->ld1 > d->ld2 ? d->ld1 : d->ld2) * 4ull;
+  const unsigned long long db = (unsigned long long)d->N * d->GH * d->GW * (unsigned long long)d->ldd * 4ull;
+  return xb <= 0xfffffff0ull && db <= 0xfffffff0ull;
+}
+
+// Slabs: a slab is one workgroup's accumulation chain, MIN_ROWS..MAX_ROWS K-steps; within that, the count that leaves the fewest
+// CUs idle in the last wave of 256 workgroups (one workgroup per CU), as wgrad_k32's plan.
+X2Plan x2_plan(const ssg_wgrad_desc* d) {
+  X2Plan p;
+  p.nj = d->Cout % 128 == 0 ? 4 : 2;
+  p.mt = (d->C1 + d->C2) / CB; p.nt = d->Cout / (32 * p.nj);
+  const long long steps = (long long)d->N * ((d->GW + KP - 1) / KP) * d->GH;
+  const long long tiles = (long long)p.mt * p.nt;
+  const long long lo = (steps + MAX_ROWS - 1) / MAX_ROWS;
+  long long hi = steps / MIN_ROWS;
+  if (hi < lo) hi = lo;
+  long long best = lo; double beff = 0;
+  for (long long sp = lo; sp <= hi && sp <= lo + 1024; ++sp) {
+    const long long wg = sp * tiles;
+    const double eff = (double)wg / (256.0 * ((wg + 255) / 256));
+    if (eff > beff + 1e-9) { beff = eff; best = sp; }
+    if (eff >= 0.97 && wg >= 256) break;
+  }
+  p.steps_per_split = (int)((steps + best - 1) / best);
+  p.splits = (int)((steps + p.steps_per_split - 1) / p.steps_per_split);
+  return p;
+}
+
+int64_t x2_ws_bytes(const ssg_wgrad_desc* d, const X2Plan& p) {
+  return (int64_t)p.splits * 9 * (d->C1 + d->C2) * d->Cout * (int64_t)sizeof(float);
+}
+
+template <int NJ>
+int x2_launch(const WgArgs& a, dim3 grid, hipStream_t st) {
+  constexpr int lds_bytes = x2_lds_bytes(NJ);
+  SSG_DYN_LDS_ONCE(wgrad_k32_x2_kernel<NJ>, lds_bytes, "wgrad bf16x2");
+  hipLaunchKernelGGL(wgrad_k32_x2_kernel<NJ>, grid, dim3(512), lds_bytes, st, a);
+  SSG_LAUNCH_CHECK();
+  return SSG_OK;
+}
+
+}  // namespace
+
+extern "C" int ssg_conv2d_wgrad_bf16x2_ok(const ssg_wgrad_desc* d) { return x2_shape_ok(d) ? 1 : 0; }
+
+extern "C" int ssg_conv2d_wgrad_bf16x2_kernel_id(const ssg_wgrad_desc* d) { return x2_shape_ok(d) ? 92 : SSG_EINVAL; }
+
+extern "C" int64_t ssg_conv2d_wgrad_bf16x2_workspace_bytes(const ssg_wgrad_desc* d) {
+  return x2_shape_ok(d) ? x2_ws_bytes(d, x2_plan(d)) : 0;
+}
+
+extern "C" int ssg_conv2d_wgrad_bf16x2_f32(const ssg_wgrad_desc* d, void* stream) {
+  SSG_REQUIRE(d && d->in1 && d->dout && d->dw_oihw && d->ws, SSG_EINVAL, "wgrad bf16x2: null pointer");
+  SSG_REQUIRE(d->C2 == 0 || d->in2, SSG_EINVAL, "wgrad bf16x2: C2 > 0 needs in2");
+  SSG_REQUIRE(x2_shape_ok(d), SSG_EINVAL,
+              "wgrad bf16x2: not the 3x3 stride-1 pad-1 weight gradient with C1 %% 64 == C2 %% 64 == Cout %% 64 == 0, GW >= 17, 32-bit byte offsets "
+              "and no in_scale (C1=%d C2=%d Cout=%d GW=%d ntaps=%d stride=%d)", d->C1, d->C2, d->Cout, d->GW, d->ntaps, d->in_sy);
+  SSG_REQUIRE(ssg_aligned16(d->in1) && ssg_aligned16(d->in2) && ssg_aligned16(d->dout) && ssg_aligned16(d->ws), SSG_EALIGN, "wgrad bf16x2: alignment");
+  const X2Plan p = x2_plan(d);
+  SSG_REQUIRE(d->ws_bytes >= x2_ws_bytes(d, p), SSG_EINVAL, "wgrad bf16x2: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  WgArgs a{};
+  a.in1 = d->in1; a.in2 = d->C2 ? d->in2 : d->in1; a.dout = d->dout; a.ws = d->ws;
+  a.C1 = d->C1; a.C2 = d->C2; a.ld1 = d->ld1; a.ld2 = d->C2 ? d->ld2 : d->ld1;
+  a.N = d->N; a.H = d->H; a.W = d->W; a.Cout = d->Cout; a.ldd = d->ldd; a.GH = d->GH; a.GW = d->GW;
+  a.in_sy = a.in_sx = 1; a.ntaps = 9;
+  a.tap_bits = ssg_pack_taps(d->dy, d->dx, 9);
+  a.M = 9 * (d->C1 + d->C2);
+  a.Ptot = (long long)d->N * d->GH * d->GW;
+  a.steps_per_split = p.steps_per_split;
+  const dim3 grid((unsigned)p.mt, (unsigned)p.nt, (unsigned)p.splits);
+  const int rc = p.nj == 4 ? x2_launch<4>(a, grid, st) : x2_launch<2>(a, grid, st);
+  if (rc != SSG_OK) return rc;
+  return ssg_wgrad_reduce_launch(d, p.splits, st);
+}

@@ -36,3 +36,24 @@ __device__ __forceinline__ void split3_4(const f32x4& u, bf16x4& p1, bf16x4& p2,
     p1[e] = h; p2[e] = m; p3[e] = (__bf16)r2;
   }
 }
+
+// Two-term split (the opt-in bf16x2 kernels): x1 = bf16_rne(x), x2 = bf16_rne(x - x1); the subtraction is exact in fp32.
+// A non-finite x (or one that rounds to bf16 infinity) makes x - x1 a NaN: such operands are conv_slow.h's.
+__device__ __forceinline__ void split2(const f32x4& u, const f32x4& v, bf16x8& p1, bf16x8& p2) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float x = e < 4 ? u[e] : v[e - 4];
+    const __bf16 h = (__bf16)x;
+    p1[e] = h; p2[e] = (__bf16)(x - (float)h);
+  }
+}
+
+// the same split for one quad of values
+__device__ __forceinline__ void split2_4(const f32x4& u, bf16x4& p1, bf16x4& p2) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float x = u[e];
+    const __bf16 h = (__bf16)x;
+    p1[e] = h; p2[e] = (__bf16)(x - (float)h);
+  }
+}

@@ -435,15 +435,16 @@ def _out_hw(h, w, kh, kw, s, pad):
 
 
 def _x1_routed(precision, stride, pad, wscale, fused):
-    """True where a conv call under `precision` asks the bf16x1 kernels first: 'bf16x1' and a unit-stride pad-1 conv of unscaled
+    """True where a conv call under `precision` asks the bf16x1 / bf16x2 kernels first: 'bf16x1' or 'bf16x2' (which of the two
+    families: the string itself) and a unit-stride pad-1 conv of unscaled
     weights (the 3x3 window and the shapes are the launchers' own predicates).  `fused` (in_affine / bwd_stats) has no bf16x1
     form: the combination is refused."""
     if precision == 'fp32':
         return False
-    if precision != 'bf16x1':
+    if precision not in ('bf16x1', 'bf16x2'):
         raise ValueError('conv: unknown precision %r (one of %s)' % (precision, ', '.join(_PRECISIONS)))
     if fused is not None:
-        raise ValueError("conv: in_affine / bwd_stats cannot be combined with precision='bf16x1'")
+        raise ValueError("conv: in_affine / bwd_stats cannot be combined with precision=%r" % (precision,))
     return stride == 1 and _pad4(pad) == (1, 1, 1, 1) and wscale is None
 
 
@@ -460,9 +461,10 @@ def _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=None, out=
     result is None (nothing launched) when the library declines.  precision='bf16x1': a unit-stride 3x3 pad-1 conv runs on
     _conv_bf16x1_impl where conv2d_bf16x1_ok holds (part is then None: that launcher has no statistics epilogue) and on the
     fp32-class kernel below where it refuses.  x1_s2 (the single-conv node only): a 3x3 stride-2 pad-1 conv without x2 / res asks
-    _conv_s2_bf16x1_impl first in the same way."""
-    if _x1_routed(precision, stride, pad, wscale, in_affine) and conv2d_bf16x1_ok(x1, weight, x2=x2, res=res):
-        y = _conv_bf16x1_impl(x1, weight, bias, act, slope, x2=x2, res=res, out=out)
+    _conv_s2_bf16x1_impl first in the same way.  precision='bf16x2': the same routing to the two-term kernel
+    (csrc/conv_halo_k32_x2.hip) for the unit-stride conv; stride 2 stays fp32-class."""
+    if _x1_routed(precision, stride, pad, wscale, in_affine) and conv2d_bf16x1_ok(x1, weight, x2=x2, res=res, family=precision):
+        y = _conv_bf16x1_impl(x1, weight, bias, act, slope, x2=x2, res=res, out=out, family=precision)
         return (y, None) if want_bn else y
     if _x1_s2_routed(precision, x1_s2, stride, pad, wscale) and x2 is None and res is None and in_affine is None:
         y = _conv_s2_bf16x1_impl(x1, weight, bias, act, slope, out=out)
@@ -499,7 +501,7 @@ def _conv_dgrad_impl(dy, weight, stride, pad, h, w, c_lo, c_hi, res=None, wscale
     _conv_dgrad_bf16x1_impl's where that takes it, and the fp32-class kernel's below where it refuses.  x1_s2 (the single-conv node
     only): a 3x3 stride-2 pad-1 gradient without res is _conv_dgrad_s2_bf16x1_impl's where all four parity classes are legal."""
     if _x1_routed(precision, stride, pad, wscale, bwd_stats):
-        dx = _conv_dgrad_bf16x1_impl(dy, weight, h, w, c_lo, c_hi, res=res)
+        dx = _conv_dgrad_bf16x1_impl(dy, weight, h, w, c_lo, c_hi, res=res, family=precision)
         if dx is not None:
             return dx
     if _x1_s2_routed(precision, x1_s2, stride, pad, wscale) and res is None and bwd_stats is None:
@@ -560,9 +562,10 @@ def _conv_dgrad_impl(dy, weight, stride, pad, h, w, c_lo, c_hi, res=None, wscale
 
 
 def _check_wgrad_s2(who, precision, wgrad_s2):
-    """The second switch's values: 'fp32' | 'bf16x1', the latter only beside precision='bf16x1'."""
-    if wgrad_s2 not in _PRECISIONS:
-        raise ValueError('%s: unknown wgrad_s2 %r (one of %s)' % (who, wgrad_s2, ', '.join(_PRECISIONS)))
+    """The second switch's values: 'fp32' | 'bf16x1', the latter only beside precision='bf16x1' (there is no two-term stride-2
+    weight gradient: 'bf16x2' is not a value of this switch, and precision='bf16x2' takes wgrad_s2='fp32' only)."""
+    if wgrad_s2 not in ('fp32', 'bf16x1'):
+        raise ValueError('%s: unknown wgrad_s2 %r (one of fp32, bf16x1)' % (who, wgrad_s2))
     if wgrad_s2 == 'bf16x1' and precision != 'bf16x1':
         raise ValueError("%s: wgrad_s2='bf16x1' needs precision='bf16x1' (got %r)" % (who, precision))
 
@@ -574,7 +577,7 @@ def _conv_wgrad_impl(x1, x2, dy, weight_shape, stride, pad, in_affine=None, prec
     wgrad_s2='bf16x1' (beside precision='bf16x1' only; the single-conv node passes it, the block nodes never do): a 3x3 stride-2
     pad-1 weight gradient without x2 / in_affine is _conv_wgrad_s2_bf16x1_impl's where that takes it."""
     if _x1_routed(precision, stride, pad, None, in_affine):
-        dw = _conv_wgrad_bf16x1_impl(x1, x2, dy, weight_shape)
+        dw = _conv_wgrad_bf16x1_impl(x1, x2, dy, weight_shape, family=precision)
         if dw is not None:
             return dw
     if (precision == 'bf16x1' and wgrad_s2 == 'bf16x1' and stride == 2 and _pad4(pad) == (1, 1, 1, 1) and x2 is None
@@ -674,7 +677,11 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, x
     stride 1 or 2 asks the one-term kernels first, in the forward and in each of its gradients, and runs today's kernel wherever
     their predicates refuse -- it never raises for a shape; `part` of a routed forward is empty.  'fp32' (default): today's launches.
     `wgrad_s2='bf16x1'` (opt-in beside precision='bf16x1', ValueError otherwise): the weight gradient of a 3x3 stride-2 pad-1 conv
-    asks the one-term stride-2 kernel first as well; 'fp32' (default) leaves it on today's kernel."""
+    asks the one-term stride-2 kernel first as well; 'fp32' (default) leaves it on today's kernel.
+    `precision='bf16x2'` (opt-in, an approximation ~2^8 times tighter than 'bf16x1': each operand split into two bf16 terms, the
+    three largest products kept, |error| <= (3 * 2^-16 + 3 * 2^-32) * conv(|x|, |w|) plus fp32 accumulation): a 3x3 pad-1 conv of
+    stride 1 asks the two-term kernels first in the forward and in each gradient, and runs today's kernel where they refuse;
+    stride 2 stays on today's kernels."""
     _lib.require_gpu(x)
     if precision not in _PRECISIONS:
         raise ValueError('conv2d: unknown precision %r (one of %s)' % (precision, ', '.join(_PRECISIONS)))
@@ -691,7 +698,17 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, x
 _X1_LABELS = {70: 'conv_halo_k32_x1_kernel<128>', 71: 'conv_halo_k32_x1_kernel<64>'}
 _X1_KIND = (_X1_LABELS, 'ssg_conv2d_bf16x1_kernel_id', _CONV_SHAPE)
 _X1_TAPS = _taps_fwd(3, 3, 1)
-_PRECISIONS = ('fp32', 'bf16x1')
+_PRECISIONS = ('fp32', 'bf16x1', 'bf16x2')
+# csrc/conv_halo_k32_x2.hip / conv_wgrad_k32_x2.hip: the two-term kernels behind precision='bf16x2', same descriptors and call
+# shapes as the one-term ones.  A family = the entry-point infix, its label tables and the cache attribute of its weight packs.
+_X2_LABELS = {90: 'conv_halo_k32_x2_kernel<128>', 91: 'conv_halo_k32_x2_kernel<64>'}
+_X2_KIND = (_X2_LABELS, 'ssg_conv2d_bf16x2_kernel_id', _CONV_SHAPE)
+_WGRAD_X2_LABELS = {92: 'wgrad_k32_x2_kernel'}
+_WGRAD_X2_KIND = (_WGRAD_X2_LABELS, 'ssg_conv2d_wgrad_bf16x2_kernel_id', _WGRAD_SHAPE)
+
+
+def _x_kind(family):
+    return _X2_KIND if family == 'bf16x2' else _X1_KIND
 
 
 class _precision(object):
@@ -715,7 +732,8 @@ class infer_precision(_precision):
     conv2d_bf16x1 where conv2d_bf16x1_ok holds (bf16 operand rounding, fp32 accumulation: an approximation) and stay on conv2d
     elsewhere.  'fp32' (the default) is today's behaviour.  Read by eval-mode module code under torch.no_grad() only: a forward
     that records a graph (autograd enabled and something requires grad) runs the fp32-class kernels whatever the mode says, and so
-    does every training path."""
+    does every training path.  'bf16x2': the same convs through conv2d(precision='bf16x2') -- two bf16 terms per operand, three
+    products (conv_halo_k32_x2_kernel), per-launch fallback to the fp32-class kernel where ssg_conv2d_bf16x2_ok declines."""
     _state = ['fp32']
 
 
@@ -747,32 +765,38 @@ def _x1_shapes_ok(x, weight, x2, res):
     return res is None or (res.dtype == torch.float32 and tuple(res.shape) == (x.shape[0], weight.shape[0], x.shape[2], x.shape[3]))
 
 
-def conv2d_bf16x1_ok(x, weight, x2=None, res=None):
+def conv2d_bf16x1_ok(x, weight, x2=None, res=None, family='bf16x1'):
     """True where conv2d_bf16x1 takes these tensors (ssg_conv2d_bf16x1_ok): a 3x3 weight, C1 % 32 == 0 and C2 % 32 == 0,
     Cout % 64 == 0, W >= 17, fp32 tensors below 4 GiB.  Launches nothing."""
     if not _x1_shapes_ok(x, weight, x2, res):
         return False
-    return call('ssg_conv2d_bf16x1_ok', C.byref(_x1_desc(x, x2, weight, res))) != 0
+    return call('ssg_conv2d_%s_ok' % family, C.byref(_x1_desc(x, x2, weight, res))) != 0
 
 
-def _x1_pack(weight, wpk, kp, fmt, transpose=0, row0=0, rows=None):
+def conv2d_bf16x2_ok(x, weight, x2=None, res=None):
+    """True where conv2d(..., precision='bf16x2') runs its forward on the two-term kernel (ssg_conv2d_bf16x2_ok): the shapes of
+    conv2d_bf16x1_ok.  Launches nothing."""
+    return conv2d_bf16x1_ok(x, weight, x2=x2, res=res, family='bf16x2')
+
+
+def _x1_pack(weight, wpk, kp, fmt, transpose=0, row0=0, rows=None, family='bf16x1'):
     """The bf16 pack of `weight` (OIHW) for format `fmt`, built from its fp32 kmode-0 matrix `wpk`; cached on the weight tensor as
     `_ssg_pack_bf16x1`, stamped like `_ssg_pack`.  transpose / row0 / rows: rows [row0, row0 + rows) of the TRANSPOSED matrix (an
     input gradient for a channel slice of a concat input); such packs are keyed (transpose, row0, rows, fmt)."""
-    cache = _stamped_cache(weight, '_ssg_pack_bf16x1')
+    cache = _stamped_cache(weight, '_ssg_pack_' + family)           # family 'bf16x2': `_ssg_pack_bf16x2`, format codes 2128 / 2064
     if rows is None:
         rows = weight.shape[0]
     key = (transpose, row0, rows, fmt) if transpose else fmt
     hit = cache.get(key)
     if hit is None:
-        nbytes = call('ssg_pack_weights_bf16x1_bytes', rows, kp, fmt)
+        nbytes = call('ssg_pack_weights_%s_bytes' % family, rows, kp, fmt)
         hit = torch.empty(nbytes // 2, dtype=torch.int16, device=weight.device)
-        call('ssg_pack_weights_bf16x1', wpk.data_ptr() + row0 * kp * 4, rows, kp, fmt, ptr(hit), stream_ptr())
+        call('ssg_pack_weights_' + family, wpk.data_ptr() + row0 * kp * 4, rows, kp, fmt, ptr(hit), stream_ptr())
         cache[key] = hit
     return hit
 
 
-def _conv_bf16x1_impl(x, weight, bias, act, slope, x2=None, res=None, out=None):
+def _conv_bf16x1_impl(x, weight, bias, act, slope, x2=None, res=None, out=None, family='bf16x1'):
     """conv2d_bf16x1 after its argument checks; `out`: an NHWC destination (a channel slice of a wider buffer in the layout tests)."""
     x = to_nhwc(x.detach())
     x2 = to_nhwc(x2.detach()) if x2 is not None else None
@@ -786,11 +810,11 @@ def _conv_bf16x1_impl(x, weight, bias, act, slope, x2=None, res=None, out=None):
     d.w = wpk.data_ptr(); d.Kp = kp; d.kmode = kmode
     d.bias = bias.data_ptr() if bias is not None else None
     d.act = int(act); d.slope = float(slope)
-    fmt = call('ssg_conv2d_bf16x1_ok', C.byref(d))
+    fmt = call('ssg_conv2d_%s_ok' % family, C.byref(d))
     if not fmt:
-        call('ssg_conv2d_bf16x1_f32', C.byref(d), None, stream_ptr())      # refused on the host, nothing launched: raises with the reason
-    pack = _x1_pack(weight, wpk, kp, fmt)
-    _timed_call(_X1_KIND, 'ssg_conv2d_bf16x1_f32', d, (ptr(pack),), (n, h, w, weight.shape[1], o, 9, 1, 1),
+        call('ssg_conv2d_%s_f32' % family, C.byref(d), None, stream_ptr())      # refused on the host, nothing launched: raises with the reason
+    pack = _x1_pack(weight, wpk, kp, fmt, family=family)
+    _timed_call(_x_kind(family), 'ssg_conv2d_%s_f32' % family, d, (ptr(pack),), (n, h, w, weight.shape[1], o, 9, 1, 1),
                 2.0 * n * h * w * o * weight.shape[1] * 9, tag=_ROLE[0])
     return out
 
@@ -830,7 +854,9 @@ class train_precision(_precision):
     node also has the stride-2 routes.  'fp32' (the default) launches exactly what runs without the context.  A node reads the mode in
     its forward and keeps it: its backward uses the forward's mode whatever is set when .backward() runs.
     wgrad_s2='bf16x1' (a second switch, default 'fp32', only beside mode 'bf16x1'): ConvolutionalBlock also hands this on, and the
-    weight gradient of its stride-2 convs asks wgrad_s2_k32_x1_kernel first.  The block nodes do not read it."""
+    weight gradient of its stride-2 convs asks wgrad_s2_k32_x1_kernel first.  The block nodes do not read it.
+    'bf16x2': the same nodes and launches on the two-term kernels (conv_halo_k32_x2_kernel, wgrad_k32_x2_kernel: each operand split
+    into two bf16 terms, three products kept); stride-2 convs stay fp32-class and wgrad_s2 must stay 'fp32'."""
     _state = ['fp32']
     _s2_state = ['fp32']
 
@@ -858,22 +884,23 @@ def train_wgrad_s2_mode():
     return train_precision._s2_state[0]
 
 
-def _conv_wgrad_bf16x1_impl(x1, x2, dy, weight_shape):
+def _conv_wgrad_bf16x1_impl(x1, x2, dy, weight_shape, family='bf16x1'):
     """Weight gradient [O, I, 3, 3] of the 3x3 stride-1 pad-1 conv of cat(x1, x2) with x and dy rounded once to bf16
-    (ssg_conv2d_wgrad_bf16x1_f32).  Returns None, with nothing launched, where ssg_conv2d_wgrad_bf16x1_ok refuses: the caller
+    (ssg_conv2d_wgrad_bf16x1_f32), or, family 'bf16x2', split into two bf16 terms (ssg_conv2d_wgrad_bf16x2_f32).  Returns None, with nothing launched, where ssg_conv2d_wgrad_bf16x1_ok refuses: the caller
     then takes _conv_wgrad_impl for this launch."""
     o, i, kh, kw = weight_shape
     if (kh, kw) != (3, 3) or tuple(dy.shape[2:]) != tuple(x1.shape[2:]) or x1.shape[1] + (x2.shape[1] if x2 is not None else 0) != i:
         return None
     d = _wgrad_desc(x1, x1.shape[1], x2, x2.shape[1] if x2 is not None else 0, dy, weight_shape, 1, _X1_TAPS)
-    if not call('ssg_conv2d_wgrad_bf16x1_ok', C.byref(d)):
+    if not call('ssg_conv2d_wgrad_%s_ok' % family, C.byref(d)):
         return None
     n, _, h, w = x1.shape
     dw = torch.empty((o, i, 3, 3), device=dy.device, dtype=torch.float32)
     d.dw_oihw = dw.data_ptr()
-    ws = _ws(call('ssg_conv2d_wgrad_bf16x1_workspace_bytes', C.byref(d)), dy.device)
+    ws = _ws(call('ssg_conv2d_wgrad_%s_workspace_bytes' % family, C.byref(d)), dy.device)
     d.ws = ws.data_ptr(); d.ws_bytes = ws.numel() * 8
-    _timed_call(_WGRAD_X1_KIND, 'ssg_conv2d_wgrad_bf16x1_f32', d, (), (n, h, w, i, o, 3, 1), 2.0 * n * h * w * o * i * 9)
+    _timed_call(_WGRAD_X2_KIND if family == 'bf16x2' else _WGRAD_X1_KIND, 'ssg_conv2d_wgrad_%s_f32' % family, d, (), (n, h, w, i, o, 3, 1),
+                2.0 * n * h * w * o * i * 9)
     return dw
 
 
@@ -902,10 +929,10 @@ def _conv_wgrad_s2_bf16x1_impl(x, dy, weight_shape):
     return dw
 
 
-def _conv_dgrad_bf16x1_impl(dy, weight, h, w, c_lo, c_hi, res=None):
+def _conv_dgrad_bf16x1_impl(dy, weight, h, w, c_lo, c_hi, res=None, family='bf16x1'):
     """Input gradient of the 3x3 stride-1 pad-1 conv for input channels [c_lo, c_hi) with dy and the weight rounded once to bf16:
     conv_halo_k32_x1_kernel on dy with rows [c_lo, c_hi) of the transposed kmode-0 pack and the taps (1 - ky, 1 - kx); `res` is
-    added in the epilogue.  Returns None, with nothing launched, where ssg_conv2d_bf16x1_ok refuses (the caller then takes
+    added in the epilogue (family 'bf16x2': conv_halo_k32_x2_kernel, two terms).  Returns None, with nothing launched, where ssg_conv2d_bf16x1_ok refuses (the caller then takes
     _conv_dgrad_impl for this launch)."""
     o, i, kh, kw = weight.shape
     n, _, oh, ow = dy.shape
@@ -915,17 +942,17 @@ def _conv_dgrad_bf16x1_impl(dy, weight, h, w, c_lo, c_hi, res=None):
     d = _x1_desc(dy, None, weight, res)
     d.Cout = rows; d.ldo = pad4(rows); d.Kp = 9 * o
     _fill_taps(d, _X1_TAPS_T)
-    if not call('ssg_conv2d_bf16x1_ok', C.byref(d)):
+    if not call('ssg_conv2d_%s_ok' % family, C.byref(d)):
         return None
     wpk, kp, kmode = _pack(weight, 1, _X1_TAPS_T, o, o)
     dx = new_nhwc(n, rows, h, w, dy.device)
     d.w = wpk.data_ptr() + c_lo * kp * 4; d.Kp = kp; d.kmode = kmode
     d.out = dx.data_ptr(); d.ldo = _ld(dx)
-    fmt = call('ssg_conv2d_bf16x1_ok', C.byref(d))
+    fmt = call('ssg_conv2d_%s_ok' % family, C.byref(d))
     if not fmt:
         return None
-    pack = _x1_pack(weight, wpk, kp, fmt, transpose=1, row0=c_lo, rows=rows)
-    _timed_call(_X1_KIND, 'ssg_conv2d_bf16x1_f32', d, (ptr(pack),), (n, h, w, o, rows, 9, 1, 1), 2.0 * n * h * w * o * rows * 9)
+    pack = _x1_pack(weight, wpk, kp, fmt, transpose=1, row0=c_lo, rows=rows, family=family)
+    _timed_call(_x_kind(family), 'ssg_conv2d_%s_f32' % family, d, (ptr(pack),), (n, h, w, o, rows, 9, 1, 1), 2.0 * n * h * w * o * rows * 9)
     return dx
 
 

@@ -41,7 +41,7 @@ def train(epoch, config, train_loader, model, criterion, optimizer, cnn_optimize
     num_class = int(config['num_classes'])
     sync = dp.grad_sync(model)
     params = [p for p in model.parameters()]
-    precision = config.get('precision', 'fp32')                              # 'bf16x1': ops.train_precision around forward and backward
+    precision = config.get('precision', 'fp32')                              # 'bf16x1' / 'bf16x2': ops.train_precision around forward and backward
     for ori_img, input, target, targets, _ in train_loader:
         input = input.cuda(non_blocking=True)
         target = target.cuda(non_blocking=True)

@@ -91,16 +91,17 @@ def gan_step(input, target, generator, discriminator, criterion, adversarial_los
              optimizer_g, optimizer_d, num_class, sync_g=None, sync_d=None, precision='fp32', d_precision='fp32',
              d_wgrad_s2='fp32'):
     """One iteration of train_seg_gan.py:182-233.  Returns device scalars (loss, iou, dice, closs, adv_g, adv_d).
-    precision: 'fp32' (default) or 'bf16x1' -- ops.train_precision around the GENERATOR's forward and the backward that reaches
-    it (its BasicBlocks then run their 3x3 convs with bf16 operands and fp32 accumulation); the discriminator, the losses, the
+    precision: 'fp32' (default), 'bf16x1' or 'bf16x2' -- ops.train_precision around the GENERATOR's forward and the backward that
+    reaches it (its BasicBlocks then run their 3x3 convs with bf16 operands -- one term, or two terms and three products -- and
+    fp32 accumulation); the discriminator, the losses, the
     parameters, the gradients and the optimizer state stay fp32 in either mode.
     d_precision: the same choice for the DISCRIMINATOR -- ops.train_precision around its three forwards (its conv nodes keep the
     mode for their backward): the 3x3 convs of its ConvolutionalBlocks then ask the one-term kernels first, stride 1 and stride 2,
     and run today's kernels where those refuse (the 3 -> 64 stem, narrow levels, the stride-2 weight gradient, spectral norm).
     d_wgrad_s2: 'fp32' (default) or 'bf16x1' -- a second switch, legal only beside d_precision='bf16x1' (ValueError otherwise, before
     anything runs): the weight gradient of the discriminator's 3x3 stride-2 convs asks the one-term wgrad_s2_k32_x1_kernel first."""
-    if d_precision not in ops._PRECISIONS:
-        raise ValueError('gan_step: unknown d_precision %r (one of %s)' % (d_precision, ', '.join(ops._PRECISIONS)))
+    if d_precision not in ('fp32', 'bf16x1'):            # there is no two-term discriminator: 'bf16x2' is the generator's alone
+        raise ValueError('gan_step: unknown d_precision %r (one of fp32, bf16x1)' % (d_precision,))
     ops._check_wgrad_s2('gan_step', d_precision, d_wgrad_s2)
     with _stage('ssg.G_forward'), ops.train_precision(precision):
         generator_output = generator(input)                                    # :188
