@@ -712,6 +712,30 @@ int ssg_sw_gather_labels_u8_f32(const uint8_t* label, int H, int W, const int32_
                                 int p_size, int out_size, int C, float* out, void* stream);
 int ssg_sw_mask_counts_u8(const uint8_t* pred, const uint8_t* gt, int C, int64_t HW, uint64_t* counts, void* stream);
 
+/* Flip / rotation test-time augmentation around the same pipeline.  A view is a D4 code k in 0 .. 7 with
+ * f = k >> 2, r = k & 3: T_k(a) = rot90(fliplr(a) if f else a, r) on a square [S, S] array, rot90 counter-clockwise
+ * (rot90(a)[i, j] = a[j, S - 1 - i]); T_k^-1(y) = fliplr(u) if f else u with u = rot90(y, 4 - r).  Moves and exact scalings only:
+ * both entries are bit for bit what the definitions say.
+ *
+ * ssg_sw_gather_patches_d4_u8_f32: ssg_sw_gather_patches_u8_f32 with `orient`, one code per launch: pixel (i, j) of patch p is
+ * pixel (i, j) of T_orient of the patch that entry writes (orient 0: the same values).  Same layout ([P, 3, out_size, out_size]
+ * NHWC, ld 4, pad lane 0), rounding steps, mean / rdenom and org / org_host contract; orient outside 0 .. 7 is refused with
+ * SSG_EINVAL and nothing is enqueued.
+ *
+ * ssg_sw_tta_reduce_f32: src holds K views of [B, C, S, S] fp32 NHWC probabilities with pixel stride ld, view k starting
+ * `slab` floats after view k - 1 (slab >= B * S * S * ld, a multiple of 4); codes is a HOST array of K ints, read before the launch
+ * and never on the device.  out[b, c] = tree-mean over k of T_codes[k]^-1(src[k, b, c]) for c < C, into a [B, C, S, S] NHWC tensor
+ * (or batch slice) with pixel stride ldo; every lane C .. ldo - 1 of out gets +0.0f, and no lane C .. ld - 1 of src reaches a
+ * result.  The mean is a balanced tree in list order in fp32 -- K = 8: (((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7))) * (1 / K),
+ * K = 4: ((q0 + q1) + (q2 + q3)) * (1 / K), K = 2: (q0 + q1) * (1 / K), K = 1: q0 -- so K equal views give back that view.
+ * Refused with SSG_EINVAL before any launch: K not in {1, 2, 4, 8}, a code outside 0 .. 7, a repeated code, C > ld or ldo,
+ * B, C or S <= 0.  out must not overlap src.  One writer per element, no atomics: deterministic. */
+int ssg_sw_gather_patches_d4_u8_f32(const uint8_t* img, int H, int W, const int32_t* org, const int32_t* org_host, int P,
+                                    int p_size, int out_size, int orient, float mean0, float mean1, float mean2,
+                                    float rdenom0, float rdenom1, float rdenom2, float* out, void* stream);
+int ssg_sw_tta_reduce_f32(const float* src, int64_t slab, int ld, int K, const int32_t* codes, int B, int C, int S,
+                          float* out, int ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -209,6 +209,8 @@ SIGNATURES = {
     'ssg_sw_merge_masks_f32_u8': [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P],
     'ssg_sw_gather_labels_u8_f32': [_P, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P],
     'ssg_sw_mask_counts_u8': [_P, _P, _I, _L, _P, _P],
+    'ssg_sw_gather_patches_d4_u8_f32': [_P, _I, _I, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P],
+    'ssg_sw_tta_reduce_f32': [_P, _L, _I, _I, _P, _I, _I, _I, _P, _I, _P],
 }
 
 # bf16 twins: same argument lists as their _f32 namesakes

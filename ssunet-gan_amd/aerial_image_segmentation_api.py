@@ -287,9 +287,10 @@ def unique_origins(org):
     return list(count.keys()), list(count.values())
 
 
-def _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, who):
+def _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, who, tta=None):
     """The device half of `segment_image` / `evaluate_image`: (prediction masks [C, H, W] uint8 on the device, ground-truth masks
     likewise or None, probabilities, origins, weights).  Every check runs before the first upload or launch."""
+    codes = None if tta is None else ops.tta_codes(tta)
     p_size, size, overlap, classes = config['patch_size'], config['input_w'], config['patch_overlap'], config['num_classes']
     if (config['input_h'], config['input_w']) != (size, size):
         raise NotImplementedError('non-square inference size')
@@ -313,9 +314,18 @@ def _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_b
     model.eval()
     gt_masks = None
     with torch.no_grad(), ops.infer_precision(precision):
-        for i in range(0, len(org), batch_size):
-            x = ops.sw_gather_patches(img, org[i:i + batch_size], p_size, size)
-            ops.sigmoid_into(model(x), probs[i:i + batch_size])
+        if codes is None:
+            for i in range(0, len(org), batch_size):
+                x = ops.sw_gather_patches(img, org[i:i + batch_size], p_size, size)
+                ops.sigmoid_into(model(x), probs[i:i + batch_size])
+        else:                                            # every view of a batch, then their mean mapped back
+            stack = ops.new_tta_stack(len(codes), min(batch_size, len(org)), classes, size, dev)
+            for i in range(0, len(org), batch_size):
+                n = len(org[i:i + batch_size])
+                for v, k in enumerate(codes):
+                    x = ops.sw_gather_patches(img, org[i:i + batch_size], p_size, size, orient=k)
+                    ops.sigmoid_into(model(x), stack[v, :n])
+                ops.sw_tta_reduce(stack[:, :n], codes, out=probs[i:i + batch_size])
         masks = ops.sw_merge_masks(probs, org, weights, p_size, img_h, img_w)
         if label_bgr is not None:                        # api.py:394-406: mask_convert per patch and class, then patch_merge
             label = torch.from_numpy(np.ascontiguousarray(label_bgr)).to(dev)
@@ -324,7 +334,7 @@ def _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_b
     return masks, gt_masks, probs, org, weights
 
 
-def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_probs=False, precision='fp32', label_bgr=None):
+def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_probs=False, precision='fp32', label_bgr=None, tta=None):
     """`segmentation_inference_full(model, *get_patched_input(...), config, False)[0]` for an image already in memory, with
     everything between the uint8 image and the uint8 masks on the device: the image is uploaded once, each batch of patches is
     cut, resized and normalised by `ops.sw_gather_patches`, `sigmoid(model(x))` stays on the device, `ops.sw_merge_masks` does
@@ -340,10 +350,17 @@ def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_pro
     lists of `segmentation_inference_full(..., gt_mask_flag=True)`, followed by the three `return_probs` items if asked for.  The
     ground-truth masks are integer arithmetic on the label alone: they depend on neither `dedupe` nor `precision`.  A label of
     another shape raises ValueError; num_classes above 3 raises ValueError (`mask_convert` has no colour for them).
+    `tta`: flip / rotation test-time augmentation, not in the reference: None (default: the statements above, nothing added),
+    'hflip', 'flips', 'd4' or a tuple of 1, 2, 4 or 8 distinct D4 codes (`ops.tta_codes`).  Each batch of patches is then gathered
+    once per code k as T_k of the patch (`ops.sw_gather_patches(..., orient=k)`), inferred, and the K probability maps are mapped
+    back by T_k^-1 and averaged by `ops.sw_tta_reduce` (balanced tree in list order, fp32) into the probabilities that are merged;
+    K forwards per patch.  It composes with `dedupe`, `precision`, `label_bgr` and `return_probs`; the ground-truth masks do not
+    depend on it.  Exact plumbing is what is tested; what it does to accuracy on a trained model is not measured here.  Anything
+    else raises ValueError before the first upload or launch.
     Not covered, as on the host path they stay with: the overlay JPGs, PNG decoding, non-square inference sizes and resize
     factors other than 1 and 2.  `evaluate_image` / `evaluate_images` turn the two mask sets into counts without a download."""
     classes = config['num_classes']
-    masks, gt_masks, probs, org, weights = _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, 'segment_image')
+    masks, gt_masks, probs, org, weights = _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, 'segment_image', tta)
     masks = masks.cpu().numpy()
     masks = [masks[c] for c in range(classes)]
     out = (masks,)
@@ -355,28 +372,32 @@ def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_pro
     return out if len(out) > 1 else masks
 
 
-def evaluate_image(model, img_bgr, label_bgr, config, batch_size=12, dedupe=True, precision='fp32', counts=None):
+def evaluate_image(model, img_bgr, label_bgr, config, batch_size=12, dedupe=True, precision='fp32', counts=None, tta=None):
     """`segment_image(..., label_bgr=label_bgr)` with both mask sets kept on the device and reduced there by
     `ops.sw_mask_counts`: returns an int64 [num_classes, 3] DEVICE tensor of pixel counts per class -- (prediction and ground
     truth, prediction, ground truth) -- added into `counts` if such a tensor is given.  No mask is downloaded and nothing
-    synchronises; read the tensor (`.cpu()`) when the numbers are needed."""
+    synchronises; read the tensor (`.cpu()`) when the numbers are needed.  `tta`: as in `segment_image`."""
+    if tta is not None:
+        ops.tta_codes(tta)
     if label_bgr is None:
         raise TypeError('evaluate_image needs a label image')
-    masks, gt_masks, _, _, _ = _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, 'evaluate_image')
+    masks, gt_masks, _, _, _ = _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, 'evaluate_image', tta)
     return ops.sw_mask_counts(masks, gt_masks, out=counts)
 
 
-def evaluate_images(model, pairs, config, batch_size=12, dedupe=True, precision='fp32'):
+def evaluate_images(model, pairs, config, batch_size=12, dedupe=True, precision='fp32', tta=None):
     """`evaluate_image` over `pairs`, an iterable of (image, label), each an HxWx3 uint8 BGR array or a path read with
     `imread_bgr`; the counts accumulate on the device and are read once at the end.  Returns a dict: `counts`, a numpy int64
     [num_classes, 3] of (intersection I, prediction P, ground truth G) pixels per class over all images, and per class the
     Python floats `iou` = (I + 1e-5) / (P + G - I + 1e-5) and `dice` = (2 I + 1e-5) / (P + G + 1e-5) -- the smoothing of
-    `metrics.iou_score`."""
+    `metrics.iou_score`.  `tta`: as in `segment_image`."""
+    if tta is not None:
+        ops.tta_codes(tta)
     counts = None
     for image, label in pairs:
         image = imread_bgr(image) if isinstance(image, (str, os.PathLike)) else image
         label = imread_bgr(label) if isinstance(label, (str, os.PathLike)) else label
-        counts = evaluate_image(model, image, label, config, batch_size, dedupe, precision, counts)
+        counts = evaluate_image(model, image, label, config, batch_size, dedupe, precision, counts, tta)
     if counts is None:
         raise ValueError('evaluate_images: no (image, label) pair given')
     counts = counts.cpu().numpy()

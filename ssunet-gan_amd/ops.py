@@ -1952,11 +1952,41 @@ def _sw_inside(host, p_size, img_h, img_w, who):
         raise ValueError('%s: a patch of size %d lies outside the %d x %d image' % (who, p_size, img_h, img_w))
 
 
-def sw_gather_patches(img_u8, origins, p_size, out_size):
+TTA_SETS = {'hflip': (0, 4), 'flips': (0, 4, 2, 6), 'd4': (0, 1, 2, 3, 4, 5, 6, 7)}
+
+
+def tta_codes(tta):
+    """The D4 codes of a test-time-augmentation request, as a tuple: `None` -> (0,); a name of TTA_SETS ('hflip': identity and
+    left-right flip; 'flips': identity, left-right, 180 degrees, up-down; 'd4': all eight); or a tuple / list of 1, 2, 4 or 8
+    distinct codes.  Code k stands for T_k(a) = rot90(fliplr(a) if k >> 2 else a, k & 3), rot90 counter-clockwise
+    (DESIGN.md 3.23).  Anything else raises ValueError."""
+    if tta is None:
+        return (0,)
+    if isinstance(tta, str):
+        if tta not in TTA_SETS:
+            raise ValueError('tta %r: expected None, one of %s, or a tuple of 1, 2, 4 or 8 distinct D4 codes' % (tta, sorted(TTA_SETS)))
+        return TTA_SETS[tta]
+    if not isinstance(tta, (tuple, list)):
+        raise ValueError('tta %r: expected None, one of %s, or a tuple of 1, 2, 4 or 8 distinct D4 codes' % (tta, sorted(TTA_SETS)))
+    codes = tuple(tta)
+    if len(codes) not in (1, 2, 4, 8):
+        raise ValueError('tta %r: %d views; the mean is a balanced tree over 1, 2, 4 or 8' % (tta, len(codes)))
+    for k in codes:
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= 7:
+            raise ValueError('tta %r: %r is no D4 code (an int in 0 .. 7)' % (tta, k))
+    if len(set(codes)) != len(codes):
+        raise ValueError('tta %r: a code is repeated' % (tta,))
+    return codes
+
+
+def sw_gather_patches(img_u8, origins, p_size, out_size, orient=0):
     """Network input of the sliding-window pipeline from the image on the device: for every origin (h1, w1) the
     p_size x p_size crop of `img_u8` ([H, W, 3] uint8, BGR), resized to out_size (p_size / out_size in {1, 2}), normalised
     and divided by 255 exactly as `get_patched_input` does on the host.  Returns [P, 3, out_size, out_size] fp32 NHWC
-    (ld 4, pad lane 0).  `origins`: P pairs (h1, w1)."""
+    (ld 4, pad lane 0).  `origins`: P pairs (h1, w1).  `orient`: a D4 code (`tta_codes`); every patch comes out as T_orient of
+    what orient = 0 gives, bit for bit, the symmetry folded into the kernel's index map.  0 is the call it has always been."""
+    if isinstance(orient, bool) or not isinstance(orient, int) or not 0 <= orient <= 7:
+        raise ValueError('sw_gather_patches: orient %r is no D4 code (an int in 0 .. 7)' % (orient,))
     _lib.require_gpu(img_u8)
     if img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3 or not img_u8.is_contiguous():
         raise TypeError('sw_gather_patches: expected a contiguous [H, W, 3] uint8 image, got %s %s' % (img_u8.dtype, tuple(img_u8.shape)))
@@ -1966,8 +1996,61 @@ def sw_gather_patches(img_u8, origins, p_size, out_size):
     _sw_inside(host, p_size, img_h, img_w, 'sw_gather_patches')
     n = host.shape[0]
     out = new_nhwc(n, 3, out_size, out_size, img_u8.device)
-    call('ssg_sw_gather_patches_u8_f32', ptr(img_u8), img_h, img_w, ptr(devo), ptr(host), n, p_size, out_size,
-         *(_sw_norm_consts() + [ptr(out), stream_ptr()]))
+    if orient == 0:
+        call('ssg_sw_gather_patches_u8_f32', ptr(img_u8), img_h, img_w, ptr(devo), ptr(host), n, p_size, out_size,
+             *(_sw_norm_consts() + [ptr(out), stream_ptr()]))
+    else:
+        call('ssg_sw_gather_patches_d4_u8_f32', ptr(img_u8), img_h, img_w, ptr(devo), ptr(host), n, p_size, out_size, orient,
+             *(_sw_norm_consts() + [ptr(out), stream_ptr()]))
+    return out
+
+
+def new_tta_stack(k, n, c, s, device):
+    """[k, n, c, s, s] fp32 over one [k, n, s, s, ld] buffer (ld = c rounded up to 4): stack[i] is an NHWC tensor like
+    `new_nhwc(n, c, s, s)`, stack[:, :m] the first m samples of every view -- what `sw_tta_reduce` takes."""
+    ld = pad4(c)
+    buf = torch.empty(k * n * s * s * ld, device=device, dtype=torch.float32)
+    return torch.empty(0, device=device, dtype=torch.float32).set_(
+        buf.untyped_storage(), 0, (k, n, c, s, s), (n * s * s * ld, s * s * ld, 1, s * ld, ld))
+
+
+def sw_tta_reduce(stack, codes, out=None):
+    """The test-time-augmentation mean on the device: `stack` is [K, B, C, S, S] fp32, view k the NHWC probabilities
+    `sigmoid(model(T_codes[k] x))` (a `new_tta_stack` tensor or a slice of one, or a list of K NHWC tensors of one shape at a
+    constant distance inside one allocation); the result is the mean over k of T_codes[k]^-1(stack[k]) -- a balanced tree of fp32
+    adds in list order times 1 / K, so K equal views give back that view bit for bit -- as [B, C, S, S] NHWC with zero pad lanes,
+    written into `out` (such a tensor, or a batch slice of one) if given.  `codes`: K = 1, 2, 4 or 8 distinct D4 codes
+    (`tta_codes`); anything else raises ValueError before any launch.  The pad lanes of the views are never read into a result."""
+    codes = tta_codes(codes)
+    if isinstance(stack, (tuple, list)):
+        views = list(stack)
+    else:
+        if stack.dim() != 5:
+            raise ValueError('sw_tta_reduce: expected a [K, B, C, S, S] stack, got %s' % (tuple(stack.shape),))
+        views = [stack[i] for i in range(stack.shape[0])]
+    if len(views) != len(codes):
+        raise ValueError('sw_tta_reduce: %d views for %d codes' % (len(views), len(codes)))
+    v0 = views[0]
+    for v in views:
+        _lib.require_gpu(v)
+    if v0.dim() != 4 or v0.shape[2] != v0.shape[3]:
+        raise ValueError('sw_tta_reduce: expected views of [B, C, S, S], got %s' % (tuple(v0.shape),))
+    ld = _ld(v0)
+    slab = (views[1].data_ptr() - v0.data_ptr()) // 4 if len(views) > 1 else 0
+    for i, v in enumerate(views):
+        if v.shape != v0.shape or v.device != v0.device or _ld(v) != ld or v.data_ptr() != v0.data_ptr() + 4 * slab * i:
+            raise ValueError('sw_tta_reduce: the views must be NHWC tensors of one shape, one pixel stride and a constant distance')
+    b, c, s, _ = v0.shape
+    if len(views) > 1 and (slab < b * s * s * ld or slab % 4):
+        raise ValueError('sw_tta_reduce: the views overlap (distance %d floats, %d each)' % (slab, b * s * s * ld))
+    if out is None:
+        out = new_nhwc(b, c, s, s, v0.device)
+    else:
+        _lib.require_gpu(out)
+        if out.shape != v0.shape or out.device != v0.device:
+            raise ValueError('sw_tta_reduce: out is %s, a view is %s' % (tuple(out.shape), tuple(v0.shape)))
+    host_codes = (C.c_int32 * len(codes))(*codes)
+    call('ssg_sw_tta_reduce_f32', ptr(v0), slab, ld, len(codes), host_codes, b, c, s, ptr(out), _ld(out), stream_ptr())
     return out
 
 
