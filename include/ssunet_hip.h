@@ -527,6 +527,22 @@ int ssg_spade_modulate_bwd_f32(const float* x, int ldx, const float* gb, int ldg
  * half of `gb` is read (ldgb >= C: a gamma-only tensor from ssg_spade_conv_modulate_f32 is fine). */
 int ssg_spade_modulate_bwd_sums_f32(const float* x, int ldx, const float* gb, int ldgb, const float* dy, int lddy, int64_t P,
                                     int C, float* dx, int lddx, float* dgb, int lddgb, double* sums, void* ws, void* stream);
+/* The lean SPADE backward: d(beta) = dy is never copied and dx = dy*(1+gamma) is never stored.
+ * ssg_spade_modulate_dgamma_sums_f32 reads x and dy only and writes dgamma = dy*x (C channels, pixel stride lddg) and the
+ * same 2C fp64 sums in the same layout, bit for bit (same products, same reduction tree, same ordered finalise);
+ * ws: ssg_bn_workspace_bytes(P, C) bytes.  16-byte aligned tensors, pixel strides multiples of 4. */
+int ssg_spade_modulate_dgamma_sums_f32(const float* x, int ldx, const float* dy, int lddy, int64_t P, int C,
+                                       float* dgamma, int lddg, double* sums, void* ws, void* stream);
+/* ssg_spade_dgrad_modulate_f32 is the launch ssg_conv2d_f32(d) makes for `d` (no residual, no bias, no activation: the input
+ * gradient of SPADE's x2map conv) whose epilogue adds dout[p][c] * (1 + gamma[p][c]) where a residual launch adds res[p][c]:
+ *   out = conv + fl(dout * fl(1 + gamma))  -- the same two operations ssg_spade_modulate_bwd_sums_f32 used for its dx, each
+ * rounded to fp32, then the residual launch's add (no fused multiply-add): the bits of the pair it replaces.
+ * dout / gamma: C = d->Cout channels, 16-byte
+ * aligned, pixel strides multiples of 4, under 2^30 elements.  ssg_spade_dgrad_modulate_ok(d): 1 where the launch of `d` runs
+ * on a kernel that has this epilogue (the thin-Cin kernels thin32_cin / thin4_cin: 4-channel input, Cout > 8, Cout % 4 == 0),
+ * else the caller keeps ssg_spade_modulate_bwd_sums_f32 and a residual launch. */
+int ssg_spade_dgrad_modulate_ok(const ssg_conv_desc* d);
+int ssg_spade_dgrad_modulate_f32(const ssg_conv_desc* d, const float* dout, int lddout, const float* gamma, int ldg, void* stream);
 /* activation backward: dx = dy * (y > 0 ? 1 : slope) (+ add) */
 int ssg_act_bwd_f32(const float* y, int ldy, const float* dy, int lddy, int64_t P, int C, int act, float slope, float* dx, int lddx, void* stream);
 /* dst[p, 0:C] = src[p, 0:C]: channel-slice copy (materialised torch.cat of > 2 tensors, archs.py:910-925) */

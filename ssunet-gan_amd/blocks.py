@@ -8,6 +8,7 @@ those gradient sums ride the dgrad kernel's residual epilogue, the ReLU masks ar
 the batch-norm backward kernels, and `torch.cat` never materialises (two-pointer convs).
 """
 import ctypes as C
+import os
 
 import torch
 
@@ -258,10 +259,94 @@ def _spade_fused_fwd(x, a, wgb, bgb, pad, out):
     return gamma
 
 
+# SSG_SPADE_BWD_LEAN (like SSG_K32): 0 = every SPADE layer runs the backward that writes dx = dout*(1+gamma) and the
+# d(gamma)|d(beta) tensor (12 passes over an [N,C,H,W] tensor per layer); 1 = the lean one (10: DESIGN.md 3.24) where its kernels
+# allow it and the tensor has at least SPADE_BWD_LEAN_MIN elements; 2 = wherever its kernels allow it (tests).
+# Below 2^20 elements the three passes the lean sequence saves are under 12 MB, under 3 us at the 5 TB/s these passes reach:
+# less than the launch of the second weight-gradient kernel and its reduce stage that the lean sequence adds.
+SPADE_BWD_LEAN = {'0': 0, '2': 2}.get(os.environ.get('SSG_SPADE_BWD_LEAN', '1'), 1)
+SPADE_BWD_LEAN_MIN = 1 << 20
+
+
+def _dgrad_taps(kh, kw, pad):
+    pt, _, pl, _ = ops._pad4(pad)
+    return [(ky, kx, pt - ky, pl - kx) for ky in range(kh) for kx in range(kw)]
+
+
+def _pack_shape(ntaps, cred_pad):
+    """(Kp, kmode) ops._pack gives a weight packed over `cred_pad` reduced channels (without packing anything)."""
+    kmode = 0 if cred_pad % 16 == 0 else 1
+    return (ntaps * cred_pad if kmode == 0 else (ntaps * cred_pad + 15) // 16 * 16), kmode
+
+
+def _conv_route_id(d, kmode):
+    """ssg_conv2d_kernel_id of descriptor `d` as ops._conv_launch would launch it (the split pack's stand-in included)."""
+    pack = call('ssg_conv2d_split_bn', C.byref(d)) if ops.MFMA_SPLIT and kmode == 0 else 0
+    d.w_split = 1 if pack else None
+    return call('ssg_conv2d_kernel_id', C.byref(d))
+
+
+def _spade_x2map_dgrad_desc(dseg, wpk_ptr, kp, kmode, taps, dx):
+    """The x2map input gradient (padded label_nc -> C channels) as ssg_conv2d_f32 launches it, without a residual."""
+    n, c, h, w = dx.shape
+    return ops._conv_desc(ops._at(dseg), ops.pad4(dseg.shape[1]), None, 0, (n, h, w), wpk_ptr, kp, kmode, None, None, ops._at(dx), c,
+                          (h, w, h, w), 1, 1, (0, 0), taps, ACT_NONE, 0.0)
+
+
+def _spade_bwd_route(x, seg, a, gb, dout, wx, wgb, pad):
+    """Which backward one SPADE layer runs -- the one place that decides it: True, the lean sequence, or
+    False, the old one (the modulate pass writes dx = dout*(1+gamma) and the d(gamma)|d(beta) tensor).  The lean sequence needs
+      * a tensor large enough to gain from it (SPADE_BWD_LEAN_MIN; not under SPADE_BWD_LEAN = 2),
+      * the x2map input gradient on a kernel with the modulated-residual epilogue (ssg_spade_dgrad_modulate_ok),
+      * each C-channel half of the gamma|beta weight gradient on the kernel the 2C-channel launch runs on
+        (ssg_conv2d_wgrad_kernel_id),
+      * the input gradient of the gamma|beta conv, reading d(gamma) and dout through the descriptor's two input pointers, on
+        the kernel the one-pointer launch over d(gamma)|d(beta) runs on (ssg_conv2d_kernel_id: same kernel, same order of
+        the reduction, same bits), and
+      * dout / gamma the epilogue's buffer descriptors can address (under 2^30 elements; nhwc_ld has checked the rest).
+    Only host-side queries: nothing is allocated, packed or launched here (the stand-in pointers are never read)."""
+    if not SPADE_BWD_LEAN:
+        return False
+    n, c, h, w = x.shape
+    nh = a.shape[1]
+    if SPADE_BWD_LEAN == 1 and n * h * w * c < SPADE_BWD_LEAN_MIN:
+        return False
+    if c % 4 or n * h * w * max(_ld(dout), _ld(gb), _ld(x)) >= 1 << 30:
+        return False
+    kh, kw = wx.shape[2], wx.shape[3]
+    taps = _dgrad_taps(kh, kw, pad)
+    kp, kmode = _pack_shape(len(taps), ops.pad4(seg.shape[1]))
+    if not call('ssg_spade_dgrad_modulate_ok', C.byref(_spade_x2map_dgrad_desc(seg, seg.data_ptr(), kp, kmode, taps, x))):
+        return False
+    gkh, gkw = wgb.shape[2], wgb.shape[3]
+
+    def wgrad_id(cout, ldd):
+        d = ops._wgrad_desc(a, ops.pad4(nh), None, 0, dout, (cout, nh, gkh, gkw), 1, ops._taps_fwd(gkh, gkw, pad))
+        d.ldd = ldd
+        d.dw_oihw = dout.data_ptr(); d.flags = 1 if ops.MFMA_SPLIT else 0
+        return call('ssg_conv2d_wgrad_kernel_id', C.byref(d))
+
+    whole = wgrad_id(2 * c, 2 * c)
+    if wgrad_id(c, c) != whole or wgrad_id(c, _ld(dout)) != whole:
+        return False
+    gtaps = _dgrad_taps(gkh, gkw, pad)
+    kp, kmode = _pack_shape(len(gtaps), 2 * c)
+
+    def dgrad_id(in1, c1, in2, c2):
+        return _conv_route_id(ops._conv_desc(in1, c1, in2, c2, (n, h, w), x.data_ptr(), kp, kmode, None, None, ops._at(a), nh,
+                                             (h, w, h, w), 1, 1, (0, 0), gtaps, ACT_NONE, 0.0), kmode)
+
+    p = x.data_ptr()
+    return dgrad_id((p, c), c, (dout.data_ptr(), _ld(dout)), c) == dgrad_id((p, 2 * c), 2 * c, None, 0)
+
+
 class _SpadeFn(torch.autograd.Function):
     """Self-conditioned SPADE: out = x*(1+gamma(a)) + beta(a), a = relu(shared(x2map(x))).
-    gamma and beta come from one conv nhidden -> 2C (concatenated weights) writing gamma|beta pixel rows; its input
-    gradient is then one launch with K = 9*2C and its weight gradient one launch whose halves are d(gamma), d(beta)."""
+    gamma and beta come from one conv nhidden -> 2C (concatenated weights) writing gamma|beta pixel rows.  Backward
+    (_spade_bwd_route says where): d(beta) = dout is not copied and dx = dout*(1+gamma) is not stored -- the modulate pass writes d(gamma) and
+    the bias sums only, the consumers of d(gamma)|d(beta) take their two halves from d(gamma) and dout, and the product joins dx
+    in the epilogue of the x2map input gradient.  Where a layer's kernels do not allow that, the old sequence: the input
+    gradient of the gamma|beta conv is one launch with K = 9*2C and its weight gradient one launch whose halves are d(gamma), d(beta)."""
 
     @staticmethod
     def forward(ctx, x, wx, bx, ws, bs, wg, bg, wb, bb, pad):
@@ -287,27 +372,59 @@ class _SpadeFn(torch.autograd.Function):
         pad = ctx.pad
         dout = to_nhwc(dout)
         n, c, h, w = x.shape
-        dxm = new_nhwc(n, c, h, w, x.device)
-        dgb = new_nhwc(n, 2 * c, h, w, x.device)
-        # modulate backward and the gamma / beta bias gradients (column sums of dgb) in one pass over the data
+        nh = a.shape[1]
+        lean = _spade_bwd_route(x, seg, a, gb, dout, wx, wgb, pad)
+        # modulate backward and the gamma / beta bias gradients (column sums of d(gamma), d(beta)) in one pass over the data
         scratch = ops._ws(call('ssg_bn_workspace_bytes', n * h * w, c), x.device)
         sums = torch.empty(2 * c, dtype=torch.float64, device=x.device)
-        # x, gamma (|beta where the conv wrote both), dout in; dx, d(gamma), d(beta) out
-        with ops._hbm('spade_modulate_bwd', 4.0 * n * h * w * c * (3 + 3)):
-            call('ssg_spade_modulate_bwd_sums_f32', ptr(x), _ld(x), ptr(gb), _ld(gb), ptr(dout), _ld(dout), n * h * w, c,
-                 ptr(dxm), _ld(dxm), ptr(dgb), _ld(dgb), ptr(sums), ptr(scratch), stream_ptr())
-        dwgb = _conv_wgrad_impl(a, None, dgb, wgb.shape, 1, pad)
+        if lean:
+            # the 10-pass sequence: neither dx = dout*(1+gamma) nor d(gamma)|d(beta) exists.  x, dout in; d(gamma) out
+            dgamma = new_nhwc(n, c, h, w, x.device)
+            with ops._hbm('spade_modulate_bwd', 4.0 * n * h * w * c * (2 + 1)):
+                call('ssg_spade_modulate_dgamma_sums_f32', ptr(x), _ld(x), ptr(dout), _ld(dout), n * h * w, c, ptr(dgamma), _ld(dgamma),
+                     ptr(sums), ptr(scratch), stream_ptr())
+            half = (c,) + tuple(wgb.shape[1:])               # the shape of the gamma conv's weight, and of the beta conv's
+            dwg = _conv_wgrad_impl(a, None, dgamma, half, 1, pad)
+            dwb = _conv_wgrad_impl(a, None, dout, half, 1, pad)
+            # the input gradient over the concatenated pack of wgb: channels [0, C) from d(gamma), [C, 2C) from dout
+            taps = _dgrad_taps(wgb.shape[2], wgb.shape[3], pad)
+            wpk, kp, kmode = ops._pack(wgb, 1, taps, 2 * c, 2 * c)
+            da = new_nhwc(n, nh, h, w, x.device)
+            ops._conv_launch(dgamma, dout, wpk, kp, kmode, 0, nh, None, None, ACT_NONE, 0.0, taps, n, h, w, h, w, h, w, 1, 1, 0, 0, da)
+            del dgamma
+        else:
+            dxm = new_nhwc(n, c, h, w, x.device)
+            dgb = new_nhwc(n, 2 * c, h, w, x.device)
+            # x, gamma (|beta where the conv wrote both), dout in; dx, d(gamma), d(beta) out
+            with ops._hbm('spade_modulate_bwd', 4.0 * n * h * w * c * (3 + 3)):
+                call('ssg_spade_modulate_bwd_sums_f32', ptr(x), _ld(x), ptr(gb), _ld(gb), ptr(dout), _ld(dout), n * h * w, c,
+                     ptr(dxm), _ld(dxm), ptr(dgb), _ld(dgb), ptr(sums), ptr(scratch), stream_ptr())
+            dwgb = _conv_wgrad_impl(a, None, dgb, wgb.shape, 1, pad)
+            dwg, dwb = dwgb[:c], dwgb[c:]
+            da = _conv_dgrad_impl(dgb, wgb, 1, pad, h, w, 0, nh)
+            del dgb
         dbias_gb = sums.float()
-        nh = a.shape[1]
-        da = _conv_dgrad_impl(dgb, wgb, 1, pad, h, w, 0, nh)
         da = _act_bwd(a, da, ACT_RELU, 0.0)
         dws = _conv_wgrad_impl(seg, None, da, ws.shape, 1, pad)
         dbs = _channel_sum(da, nh)
         dseg = _conv_dgrad_impl(da, ws, 1, pad, h, w, 0, seg.shape[1])
         dwx = _conv_wgrad_impl(x, None, dseg, wx.shape, 1, pad)
         dbx = _channel_sum(dseg, seg.shape[1])
-        dx = _conv_dgrad_impl(dseg, wx, 1, pad, h, w, 0, c, res=dxm) if ctx.needs_input_grad[0] else None
-        return dx, dwx, dbx, dws, dbs, dwgb[:c], dbias_gb[:c], dwgb[c:], dbias_gb[c:], None
+        dx = None
+        if ctx.needs_input_grad[0] and lean:
+            # dx = dgrad(dseg, wx) + dout*(1+gamma): the product is formed in the launch's epilogue (only the gamma half of gb is read)
+            kh, kw = wx.shape[2], wx.shape[3]
+            taps = _dgrad_taps(kh, kw, pad)
+            cred = ops.pad4(wx.shape[0])
+            wpk, kp, kmode = ops._pack(wx, 1, taps, cred, cred)
+            dx = new_nhwc(n, c, h, w, x.device)
+            d = _spade_x2map_dgrad_desc(dseg, wpk.data_ptr(), kp, kmode, taps, dx)
+            label = ops._CONV_LABELS.get(call('ssg_conv2d_kernel_id', C.byref(d)), '?') if ops.PROFILE is not None else None
+            with ops._Timed(label, 2.0 * n * h * w * c * wx.shape[0] * kh * kw):
+                call('ssg_spade_dgrad_modulate_f32', C.byref(d), ptr(dout), _ld(dout), ptr(gb), _ld(gb), stream_ptr())
+        elif ctx.needs_input_grad[0]:
+            dx = _conv_dgrad_impl(dseg, wx, 1, pad, h, w, 0, c, res=dxm)
+        return dx, dwx, dbx, dws, dbs, dwg, dbias_gb[:c], dwb, dbias_gb[c:], None
 
 
 def spade_self(x, x2map, shared, gamma, beta):

@@ -203,6 +203,46 @@ __global__ __launch_bounds__(RED_BLOCK) void modulate_bwd_sums_kernel(
   }
 }
 
+// The lean form of the pass above: dgamma = dy*x and the same two column sums, nothing else.  d(beta) is dy itself (its
+// consumers read dy), and dx = dy*(1+gamma) is formed in the epilogue of the x2map input gradient
+// (ssg_spade_dgrad_modulate_f32), so gamma is not read here: 2 reads + 1 write instead of 3 + 3.  Same geometry, same
+// products, same accumulation order as modulate_bwd_sums_kernel: dgamma and the partial rows carry the same bits.
+__global__ __launch_bounds__(RED_BLOCK) void modulate_dgamma_sums_kernel(
+    const float* __restrict__ x, int ldx, const float* __restrict__ dy, int lddy, long long P, int C,
+    float* __restrict__ dg_out, int lddg, int TQ, int PR, long long rows_per_part, double* __restrict__ part /* [parts][2][C] */) {
+  __shared__ double red[2][RED_BLOCK][4];
+  const int tid = threadIdx.x;
+  const int tq = tid % TQ, pr = tid / TQ;
+  const int cq = blockIdx.y * TQ + tq;
+  const int CQ = C / 4;
+  const bool cok = cq < CQ;
+  const long long p0 = (long long)blockIdx.x * rows_per_part;
+  long long p1 = p0 + rows_per_part; if (p1 > P) p1 = P;
+  double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+  if (cok) {
+    for (long long p = p0 + pr; p < p1; p += PR) {
+      const f32x4 xv = *(const f32x4*)(x + p * ldx + 4 * cq);
+      const f32x4 d = *(const f32x4*)(dy + p * lddy + 4 * cq);
+      const f32x4 dg = d * xv;
+      st4(dg_out + p * lddg + 4 * cq, dg);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { s1[e] += (double)dg[e]; s2[e] += (double)d[e]; }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { red[0][tid][e] = s1[e]; red[1][tid][e] = s2[e]; }
+  __syncthreads();
+  if (pr == 0 && cok) {
+    double a1[4] = {0, 0, 0, 0}, a2[4] = {0, 0, 0, 0};
+    for (int r = 0; r < PR; ++r)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { a1[e] += red[0][r * TQ + tq][e]; a2[e] += red[1][r * TQ + tq][e]; }
+    double* dst = part + (size_t)blockIdx.x * 2 * C;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { dst[4 * cq + e] = a1[e]; dst[C + 4 * cq + e] = a2[e]; }
+  }
+}
+
 // Second stage: 32 channels x 32 part-lanes per block; each lane adds every 32nd partial row in
 // row order, then the 32 lane sums are added in lane order -> fixed summation order (bitwise
 // reproducible), 1/32 of the serial chain of a one-thread-per-channel loop.
@@ -620,6 +660,23 @@ extern "C" int ssg_spade_modulate_bwd_sums_f32(const float* x, int ldx, const fl
                      (long long)P, C, dx, lddx, dgb, lddgb, g.TQ, g.PR, g.rows_per_part, part);
   SSG_LAUNCH_CHECK();
   // sums[0:C] = sum dgamma, sums[C:2C] = sum dbeta (ssg_bn_workspace_bytes(P, C) bytes of workspace)
+  hipLaunchKernelGGL(col_reduce_final_kernel, dim3((unsigned)((C + 31) / 32)), dim3(32 * FIN_LANES), 0, st, part, g.parts, C, C, sums, nullptr, 0.0, BnFin{}, 0.0);
+  SSG_LAUNCH_CHECK();
+  return SSG_OK;
+}
+
+extern "C" int ssg_spade_modulate_dgamma_sums_f32(const float* x, int ldx, const float* dy, int lddy, int64_t P, int C,
+                                                  float* dgamma, int lddg, double* sums, void* ws, void* stream) {
+  SSG_REQUIRE(x && dy && dgamma && sums && ws && P > 0 && C > 0 && C % 4 == 0 && ldx >= C && lddy >= C && lddg >= C &&
+              ldx % 4 == 0 && lddy % 4 == 0 && lddg % 4 == 0, SSG_EINVAL, "modulate_dgamma_sums: bad args");
+  SSG_REQUIRE(ssg_aligned16(x) && ssg_aligned16(dy) && ssg_aligned16(dgamma), SSG_EALIGN, "modulate_dgamma_sums: 16-byte alignment");
+  const RedGeom g = red_geom(P, C);
+  double* part = (double*)ws;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(modulate_dgamma_sums_kernel, dim3((unsigned)g.parts, (unsigned)g.groups), dim3(RED_BLOCK), 0, st, x, ldx, dy, lddy,
+                     (long long)P, C, dgamma, lddg, g.TQ, g.PR, g.rows_per_part, part);
+  SSG_LAUNCH_CHECK();
+  // the layout and the finalise of ssg_spade_modulate_bwd_sums_f32: sums[0:C] = sum dgamma, sums[C:2C] = sum dy
   hipLaunchKernelGGL(col_reduce_final_kernel, dim3((unsigned)((C + 31) / 32)), dim3(32 * FIN_LANES), 0, st, part, g.parts, C, C, sums, nullptr, 0.0, BnFin{}, 0.0);
   SSG_LAUNCH_CHECK();
   return SSG_OK;

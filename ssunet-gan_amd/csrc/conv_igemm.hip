@@ -397,6 +397,21 @@ extern "C" int ssg_conv2d_bwd_stats_ok(const ssg_conv_desc* d) { const ConvPlan 
 extern "C" int64_t ssg_conv2d_workspace_bytes(const ssg_conv_desc* d) { const ConvPlan p = plan_conv(d); return p.rc == SSG_OK ? p.ws_bytes : 0; }
 extern "C" int ssg_conv2d_kernel_id(const ssg_conv_desc* d) { const ConvPlan p = plan_conv(d); return p.rc == SSG_OK ? p.id : p.rc; }
 
+// SPADE backward (include/ssunet_hip.h): the launch ssg_conv2d_f32(d) makes for a descriptor without residual, with the product
+// dout * (1 + gamma) added in its epilogue.  Only the thin-Cin kernels of conv_thin4.hip have that epilogue.
+extern "C" int ssg_spade_dgrad_modulate_ok(const ssg_conv_desc* d) {
+  if (!d || d->res || d->bias || d->act != SSG_ACT_NONE || d->in_scale || d->bwd_x || d->parity_merge) return 0;
+  const ConvPlan p = plan_conv(d);
+  return p.rc == SSG_OK && p.kind == KIND_THIN4 && ssg_thin4_conv_mod_ok(d, p.variant);
+}
+
+extern "C" int ssg_spade_dgrad_modulate_f32(const ssg_conv_desc* d, const float* dout, int lddout, const float* gamma, int ldg, void* stream) {
+  SSG_REQUIRE(ssg_spade_dgrad_modulate_ok(d), SSG_EINVAL,
+              "spade_dgrad_modulate: the launch of this descriptor has no modulated-residual epilogue (ssg_spade_dgrad_modulate_ok == 0)");
+  const ConvPlan p = plan_conv(d);
+  return ssg_thin4_conv_launch_mod(d, p.variant, dout, lddout, gamma, ldg, (hipStream_t)stream);
+}
+
 // rows of the batch-norm partial buffer the launch for `d` writes (one per pixel tile), or 0 when the kernel has no statistics
 // epilogue (thin / register-staged kernels, split-K launches): the caller then runs ssg_bn_stats_f32 instead
 extern "C" int ssg_conv2d_bnpart_rows(const ssg_conv_desc* d) {

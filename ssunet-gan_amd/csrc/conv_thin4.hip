@@ -26,6 +26,7 @@ struct T4Args {
   int rh;                    // thin-Cout rows form: output rows per workgroup
   int nt_store;              // thin-Cin: non-temporal output stores (output larger than the caches)
   float* gsave; int ldg;     // thin32 SPADE mode: where gamma (+ bias) goes (the backward needs it), pixel stride
+  const float* in2; int ld2; // thin-Cout TWO: the reduced channels [C/2, C) come from this tensor (ssg_conv_desc.in2, C1 == C2)
 };
 
 constexpr int RH_CIN = 16;       // rows per work unit (thin-Cin): a 4-pixel-wide strip marched downwards
@@ -40,6 +41,17 @@ __device__ __forceinline__ float act_apply(float v, int act, float slope) {
   if (act == SSG_ACT_RELU) return v < 0.f ? 0.f : v;
   if (act == SSG_ACT_LRELU) return v > 0.f ? v : v * slope;
   return v;
+}
+
+// The residual term of the SPADE backward (ssg_spade_dgrad_modulate_f32), shared by the thin-Cin epilogues: where a launch with a
+// residual tensor adds res = dy * (1 + gamma), written by the modulate pass and read back, this forms the product here with the
+// same two operations (add, multiply: both rounded) and adds it the same way, so the launch gives the bits of the pair it
+// replaces.  hipcc would contract the multiply into the following add (one rounding less, other bits: after three training
+// steps the IoU of the benchmark moved in its fifth digit); the empty asm keeps the product a value of its own.
+__device__ __forceinline__ float t4_mod_add(float t, float dy, float gamma) {
+  float r = dy * (1.f + gamma);
+  asm("" : "+v"(r));
+  return t + r;
 }
 
 // Both kernels march a 4-pixel-wide strip down the image with a ring of KS+1 input rows in registers:
@@ -57,7 +69,9 @@ __device__ __forceinline__ float act_apply(float v, int act, float slope) {
 // the just-issued output store and every prefetched row each iteration (the kernel ran at 2.3 TB/s whatever PF was).  The
 // residual now comes through the buffer descriptor path (OOB offset instead of a branch), one row ahead, so the compiler
 // emits counted waits only.
-template <int KS, int PF, bool HAS_RES>
+// MODRES (SPADE backward, ssg_spade_dgrad_modulate_f32): the residual is not a tensor but the product dy * (1 + gamma) of
+// a.res = dy and a.gsave = gamma (read here, pixel stride a.ldg), added by t4_mod_add; both come through the same descriptor path.
+template <int KS, int PF, bool HAS_RES, bool MODRES = false>
 __global__ __launch_bounds__(256) void thin4_cin_kernel(const T4Args a) {
   constexpr int R = KS / 2, NT = KS * KS, RING = KS + PF;
   const int lane = threadIdx.x & 63, j = lane & 3, b = lane >> 2;
@@ -69,6 +83,8 @@ __global__ __launch_bounds__(256) void thin4_cin_kernel(const T4Args a) {
   const unsigned ldb = (unsigned)a.ld * 4u;
   const auto res_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(HAS_RES ? a.res : a.in), 0,
                                                         (int)(npix * (unsigned)(HAS_RES ? a.ldr : a.ld) * 4u), 0x00020000);
+  const auto gm_rs = __builtin_amdgcn_make_buffer_rsrc(MODRES ? a.gsave : const_cast<float*>(a.in), 0,
+                                                       (int)(npix * (unsigned)(MODRES ? a.ldg : a.ld) * 4u), 0x00020000);
 
   // A operand: this lane's output channel, all taps x 4 channels (kmode 1: k = t*4 + c)
   const int co = cg * 64 + lane;
@@ -120,7 +136,13 @@ __global__ __launch_bounds__(256) void thin4_cin_kernel(const T4Args a) {
       const bool ok = x < a.W && st_ok && yy < y1;
       return ldbuf4(res_rs, ok ? ((unsigned)((n * a.H + yy) * a.W + x) * (unsigned)a.ldr + (unsigned)cb) * 4u : OOB);
     };
+    f32x4 gvr[MODRES ? RING : 1];
+    auto load_gm = [&](int yy) -> f32x4 {
+      const bool ok = x < a.W && st_ok && yy < y1;
+      return ldbuf4(gm_rs, ok ? ((unsigned)((n * a.H + yy) * a.W + x) * (unsigned)a.ldg + (unsigned)cb) * 4u : OOB);
+    };
     if (HAS_RES) rvr[0] = load_res(y0);
+    if (MODRES) gvr[0] = load_gm(y0);
     for (int y = y0; y < y1; y += RING) {
 #pragma unroll
       for (int r = 0; r < RING; ++r) {
@@ -135,6 +157,8 @@ __global__ __launch_bounds__(256) void thin4_cin_kernel(const T4Args a) {
           const size_t pix = (size_t)(n * a.H + y + r) * a.W + x;
           f32x4 rv = {0.f, 0.f, 0.f, 0.f};
           if (HAS_RES) { rvr[(r + 1) % RING] = load_res(y + r + 1); rv = rvr[r]; }
+          f32x4 gv = {0.f, 0.f, 0.f, 0.f};
+          if (MODRES) { gvr[(r + 1) % RING] = load_gm(y + r + 1); gv = gvr[r]; }
           // two accumulator chains (even / odd k) keep dependent MFMAs apart
           f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -146,7 +170,14 @@ __global__ __launch_bounds__(256) void thin4_cin_kernel(const T4Args a) {
                 acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[q * KS + e][c], v[(r + q) % RING][e][c], acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wv[q * KS + e][c + 1], v[(r + q) % RING][e][c + 1], acc1, 0, 0, 0);
               }
-          const f32x4 t = acc0 + acc1 + bv + rv * cmask;
+          f32x4 t;
+          if (MODRES) {
+            t = acc0 + acc1 + bv;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) t[i] = t4_mod_add(t[i], rv[i] * cmask[i], gv[i]);
+          } else {
+            t = acc0 + acc1 + bv + rv * cmask;
+          }
 #pragma unroll
           for (int i = 0; i < 4; ++i) pend[i] = (t[i] < 0.f ? (is_relu ? 0.f : t[i] * neg_slope) : t[i]) * cmask[i];
           pend_ptr = (x < a.W && st_ok) ? a.out + pix * a.ldo + cb : nullptr;
@@ -180,11 +211,12 @@ constexpr int RH_K36 = 16;       // output rows per work unit
 // C..2C-1] (a.Cout = 2C), the wave's two N-fragments are gamma and beta of the SAME 32 channels, `res` is the tensor being
 // modulated: out = x * (1 + gamma) + beta, and gamma goes to a.gsave.  The [N,2C,H,W] gamma|beta tensor and the separate
 // modulate pass (3 reads + 1 write of C channels) never exist.
+// 3: MODE 1 whose residual is the product dy * (1 + gamma) (SPADE backward, t4_mod_add): `res` = dy, a.gsave = gamma, READ here.
 // CIN = 4: the lane half h owns the channel pair {2h, 2h+1} of a tap (8-byte loads, 18 K-steps); CIN = 8 (SPADE at the 256^2
 // level, nhidden = 8): the quad {4h .. 4h+3} (16-byte loads, 36 K-steps, 72 weight registers).
 template <int MODE, int PF, bool NT, int CIN = 4>
 __global__ __launch_bounds__(256) void thin32_cin_kernel(const T4Args a) {
-  constexpr bool HAS_RES = MODE >= 1, SPADE = MODE == 2;
+  constexpr bool HAS_RES = MODE >= 1, SPADE = MODE == 2, MODRES = MODE == 3;
   constexpr int CH = CIN / 2;               // channels per lane half and tap
   typedef float vrow_t __attribute__((ext_vector_type(CH)));
   constexpr int AUX = NT ? 2 : 0;           // non-temporal stores for outputs far larger than the caches
@@ -198,7 +230,8 @@ __global__ __launch_bounds__(256) void thin32_cin_kernel(const T4Args a) {
   const auto out_rs = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (int)(npix * (unsigned)a.ldo * 4u), 0x00020000);
   const auto res_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(HAS_RES ? a.res : a.in), 0,
                                                         (int)(npix * (unsigned)(HAS_RES ? a.ldr : a.ld) * 4u), 0x00020000);
-  const auto g_rs = __builtin_amdgcn_make_buffer_rsrc(SPADE ? a.gsave : a.out, 0, (int)(npix * (unsigned)(SPADE ? a.ldg : a.ldo) * 4u), 0x00020000);
+  const auto g_rs = __builtin_amdgcn_make_buffer_rsrc((SPADE || MODRES) ? a.gsave : a.out, 0,
+                                                      (int)(npix * (unsigned)((SPADE || MODRES) ? a.ldg : a.ldo) * 4u), 0x00020000);
   const unsigned ldb = (unsigned)a.ld * 4u, ldob = (unsigned)a.ldo * 4u, ldrb = (unsigned)a.ldr * 4u, ldgb = (unsigned)a.ldg * 4u;
   const int Cmod = a.Cout >> 1;            // SPADE: channels of x / out / gamma
 
@@ -206,6 +239,7 @@ __global__ __launch_bounds__(256) void thin32_cin_kernel(const T4Args a) {
   float wB[2][9 * CH], bv[2], keep[2];       // keep = 0 for the pad lanes [Cout, pad4(Cout)): written as 0
   unsigned vo_out[2], vo_res[2];         // per-lane part of the byte offset (pixel 4*h of the strip, this lane's channel) or OOB
   unsigned vo_g = OOB;
+  unsigned vo_gm[2] = {OOB, OOB};        // MODRES: the same for the gamma rows
 #pragma unroll
   for (int f = 0; f < 2; ++f) {
     const int cm = cg * 32 + l31;          // SPADE: the modulated channel of this lane
@@ -224,6 +258,7 @@ __global__ __launch_bounds__(256) void thin32_cin_kernel(const T4Args a) {
     vo_out[f] = cok ? 4u * (unsigned)h * ldob + (unsigned)cch * 4u : OOB;
     vo_res[f] = cok ? 4u * (unsigned)h * ldrb + (unsigned)cch * 4u : OOB;
     if (SPADE) vo_g = cok ? 4u * (unsigned)h * ldgb + (unsigned)cch * 4u : OOB;
+    if (MODRES) vo_gm[f] = cok ? 4u * (unsigned)h * ldgb + (unsigned)cch * 4u : OOB;
   }
   const bool is_relu = a.act == SSG_ACT_RELU;
   const float neg_slope = a.act == SSG_ACT_LRELU ? a.slope : 1.f;
@@ -277,6 +312,26 @@ __global__ __launch_bounds__(256) void thin32_cin_kernel(const T4Args a) {
       const unsigned rowpix = (unsigned)((n * a.H + yy) * a.W + x0);  // loop-invariant, the rest rides the scalar offset
       float rv[2][16];
       const unsigned (&vo)[2] = vo_out; const unsigned (&vr)[2] = vo_res;
+      if (MODRES) {                      // one fragment at a time: 16 dy + 16 gamma values in flight
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          float gv[16];
+#pragma unroll
+          for (int q = 0; q < 16; ++q) {
+            const unsigned pq = rowpix + (unsigned)((q & 3) + 8 * (q >> 2));
+            rv[0][q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(res_rs, vr[f], (int)(pq * ldrb), 0));
+            gv[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(g_rs, vo_gm[f], (int)(pq * ldgb), 0));
+          }
+#pragma unroll
+          for (int q = 0; q < 16; ++q) {
+            float t = t4_mod_add(acc[f][q] + bv[f], rv[0][q], gv[q]);
+            t = (t < 0.f ? (is_relu ? 0.f : t * neg_slope) : t) * keep[f];
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t), out_rs, vo[f],
+                                                  (int)((rowpix + (unsigned)((q & 3) + 8 * (q >> 2))) * ldob), AUX);
+          }
+        }
+        return;
+      }
       if (HAS_RES) {
 #pragma unroll
         for (int f = 0; f < (SPADE ? 1 : 2); ++f)
@@ -328,7 +383,12 @@ __global__ __launch_bounds__(256) void thin32_cin_kernel(const T4Args a) {
         for (int q = 0; q < 16; ++q) {
           if ((inw >> q) & 1u) {
             float t = acc[f][q] + bv[f];
-            if (HAS_RES) t += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+            if (MODRES) {
+              const unsigned pq = rowpix + (unsigned)((q & 3) + 8 * (q >> 2));
+              const float dv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(res_rs, vo_res[f], (int)(pq * ldrb), 0));
+              const float gv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(g_rs, vo_gm[f], (int)(pq * ldgb), 0));
+              t = t4_mod_add(t, dv, gv);
+            } else if (HAS_RES) t += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                 res_rs, vo_res[f], (int)((rowpix + (unsigned)((q & 3) + 8 * (q >> 2))) * ldrb), 0));
             t = (t < 0.f ? (is_relu ? 0.f : t * neg_slope) : t) * keep[f];
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t), out_rs, vo_out[f],
@@ -474,7 +534,11 @@ __device__ __forceinline__ void t4_fold_store(const T4Args& a, const f32x4* acc,
 
 // ------------------------------------------------------------------ thin-Cout: Cout <= 4*NG, C % 64 == 0
 // NG = 2 (Cout 5..8, e.g. the 128 -> 8 gamma/beta input gradients) runs two A-operand sets over the same loaded rows.
-template <int KS, int NG>
+// TWO: the 64-channel chunks of the second half of the reduction come from a.in2 (the lean SPADE backward reads d(gamma) and
+// dout where it read d(gamma)|d(beta)): same chunk order, same MFMAs, same fold -- the bits of the one-tensor launch.  (As two
+// copies of the chunk loop, one per tensor, the 256 -> 8 launch at 16 x 256^2 took 0.221 ms against 0.186 ms for the one-tensor
+// kernel; the selects below keep one copy.)
+template <int KS, int NG, bool TWO = false>
 __global__ __launch_bounds__(256) void thin4_cout_kernel(const T4Args a) {
   constexpr int R = KS / 2, NT = KS * KS, S = RH_COUT, RING = KS + 1;
   const int lane = threadIdx.x & 63, j = lane & 3, b = lane >> 2;
@@ -482,8 +546,9 @@ __global__ __launch_bounds__(256) void thin4_cout_kernel(const T4Args a) {
   if (wg >= a.waves_per_group) return;
   const unsigned npix = (unsigned)(a.N * a.H * a.W);
   const auto in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, (int)(npix * (unsigned)a.ld * 4u), 0x00020000);
-  const unsigned ldb = (unsigned)a.ld * 4u;
+  const unsigned ldb = (unsigned)a.ld * 4u, ldb2 = (unsigned)(TWO ? a.ld2 : a.ld) * 4u;
   const int nchunks = a.C >> 6;
+  const int nch1 = TWO ? nchunks >> 1 : nchunks;       // chunks read from a.in
   // A operand row: lane 4b+i supplies w[co = 4g + i]
   // after the butterfly lane (b, j) owns outputs (row s = b >> 1, pixel j, channels 4g + 2*(b&1), +1)
   const int my_s = b >> 1, my_c = 2 * (b & 1);
@@ -499,13 +564,15 @@ __global__ __launch_bounds__(256) void thin4_cout_kernel(const T4Args a) {
     const int yb = r0 % a.ybands, n = r0 / a.ybands;
     const int x = xs * 4 + j;
     const int y0 = yb * S;
-    unsigned coloff[KS];
+    unsigned coloff[KS], coloff2[TWO ? KS : 1];
 #pragma unroll
     for (int e = 0; e < KS; ++e) {
       const int ix = x + e - R;
       coloff[e] = (unsigned)ix < (unsigned)a.W ? (unsigned)ix * ldb + 16u * b : OOB;
+      if (TWO) coloff2[e] = (unsigned)ix < (unsigned)a.W ? (unsigned)ix * ldb2 + 16u * b : OOB;
     }
     const unsigned imgoff = (unsigned)(n * a.H) * (unsigned)a.W * ldb;
+    const unsigned imgoff2 = (unsigned)(n * a.H) * (unsigned)a.W * ldb2;
     f32x4 accg[NG][S];
 #pragma unroll
     for (int g = 0; g < NG; ++g)
@@ -513,6 +580,15 @@ __global__ __launch_bounds__(256) void thin4_cout_kernel(const T4Args a) {
       for (int s = 0; s < S; ++s) accg[g][s] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int ch = 0; ch < nchunks; ++ch) {
       const int c0 = ch * 64 + 4 * b;                // this lane's 4 reduced channels
+      // TWO: which tensor this chunk's rows come from -- wave-uniform selects, one copy of the loop body
+      const bool second = TWO && ch >= nch1;
+      const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(second ? a.in2 : a.in), 0,
+                                                        (int)(npix * (second ? ldb2 : ldb)), 0x00020000);
+      const unsigned rowb = second ? ldb2 : ldb;
+      const unsigned chunkoff = (second ? imgoff2 : imgoff) + (unsigned)(second ? ch - nch1 : ch) * 256u;
+      unsigned co[KS];
+#pragma unroll
+      for (int e = 0; e < KS; ++e) co[e] = second ? coloff2[e] : coloff[e];
       f32x4 wv[NG][NT];
 #pragma unroll
       for (int p = 0; p < NT; ++p) {
@@ -526,9 +602,15 @@ __global__ __launch_bounds__(256) void thin4_cout_kernel(const T4Args a) {
       }
       auto load_row = [&](f32x4* dst, int iy) {
         const bool rok = (unsigned)iy < (unsigned)a.H;
-        const unsigned ro = imgoff + (unsigned)iy * (unsigned)a.W * ldb + (unsigned)ch * 256u;
+        if constexpr (TWO) {
+          const unsigned ro = chunkoff + (unsigned)iy * (unsigned)a.W * rowb;
 #pragma unroll
-        for (int e = 0; e < KS; ++e) dst[e] = ldbuf4(in_rs, (rok && coloff[e] != OOB) ? ro + coloff[e] : OOB);
+          for (int e = 0; e < KS; ++e) dst[e] = ldbuf4(rs, (rok && co[e] != OOB) ? ro + co[e] : OOB);
+        } else {
+          const unsigned ro = imgoff + (unsigned)iy * (unsigned)a.W * ldb + (unsigned)ch * 256u;
+#pragma unroll
+          for (int e = 0; e < KS; ++e) dst[e] = ldbuf4(in_rs, (rok && coloff[e] != OOB) ? ro + coloff[e] : OOB);
+        }
       };
       f32x4 v[RING][KS];
 #pragma unroll
@@ -570,15 +652,18 @@ __global__ __launch_bounds__(256) void thin4_cout_kernel(const T4Args a) {
 // tile in lane group g) and the sum's read (rows q * Cout + co, four consecutive co in the four lane groups) both spread
 // over all banks.  RING = 4 slots need one barrier per row (the slot written next is never one of the three being read); the
 // 80-row form (Cout 5..8) keeps 3 slots inside the 64 KiB of static LDS and pays a second barrier.
-template <int MT, int KC>
+// TWO: the second half of the KC 64-channel chunks is read from a.in2 (see thin4_cout_kernel); which load reads which tensor is
+// known at compile time.
+template <int MT, int KC, bool TWO = false>
 __global__ __launch_bounds__(256) void thin4_cout_kernel_rows(const T4Args a) {
-  constexpr int RING = MT >= 5 ? 3 : 4, NL = KC * 4;
+  constexpr int RING = MT >= 5 ? 3 : 4, NL = KC * 4, NL1 = TWO ? NL / 2 : NL;
   __shared__ float P[RING][MT * 16][64];
   const int lane = threadIdx.x & 63, p = lane & 15, g = lane >> 4;
   const int wv_id = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const unsigned npix = (unsigned)(a.N * a.H * a.W);
   const auto in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, (int)(npix * (unsigned)a.ld * 4u), 0x00020000);
-  const unsigned ldb = (unsigned)a.ld * 4u;
+  const unsigned ldb = (unsigned)a.ld * 4u, ldb2 = (unsigned)(TWO ? a.ld2 : a.ld) * 4u;
+  const auto in2_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(TWO ? a.in2 : a.in), 0, (int)(npix * ldb2), 0x00020000);
   const int u = blockIdx.x;
   const int xs = u % a.strips; const int r0 = u / a.strips;
   const int yb = r0 % a.ybands, n = r0 / a.ybands;
@@ -603,11 +688,18 @@ __global__ __launch_bounds__(256) void thin4_cout_kernel_rows(const T4Args a) {
   }
   const unsigned coloff = (unsigned)x < (unsigned)a.W ? (unsigned)x * ldb + 16u * (unsigned)g : OOB;
   const unsigned imgoff = (unsigned)(n * a.H) * (unsigned)a.W * ldb;
+  const unsigned coloff2 = (unsigned)x < (unsigned)a.W ? (unsigned)x * ldb2 + 16u * (unsigned)g : OOB;
+  const unsigned imgoff2 = (unsigned)(n * a.H) * (unsigned)a.W * ldb2;
   auto load_row = [&](f32x4* dst, int iy) {
     const bool rok = (unsigned)iy < (unsigned)a.H && coloff != OOB;
     const unsigned ro = imgoff + (unsigned)iy * (unsigned)a.W * ldb + coloff;
 #pragma unroll
-    for (int l = 0; l < NL; ++l) dst[l] = ldbuf4(in_rs, rok ? ro + 64u * (unsigned)l : OOB);
+    for (int l = 0; l < NL1; ++l) dst[l] = ldbuf4(in_rs, rok ? ro + 64u * (unsigned)l : OOB);
+    if constexpr (TWO) {
+      const unsigned ro2 = imgoff2 + (unsigned)iy * (unsigned)a.W * ldb2 + coloff2;
+#pragma unroll
+      for (int l = NL1; l < NL; ++l) dst[l] = ldbuf4(in2_rs, rok ? ro2 + 64u * (unsigned)(l - NL1) : OOB);
+    }
   };
   // the sum: lane group g owns output channel 4 * pass + g of pixel column `col`
   const int cpad = (a.Cout + 3) & ~3;
@@ -698,15 +790,25 @@ bool window_taps(const ssg_conv_desc* d, int* tapidx) {
 
 // 0 = no; 3 = thin-Cin (in has 4 channels); 4 = thin-Cout (Cout <= 8, Cin % 64 == 0).
 int ssg_thin4_conv_kind(const ssg_conv_desc* d) {
-  if (d->C2 != 0 || d->in_sy != 1 || d->in_sx != 1 || d->out_sy != 1 || d->out_sx != 1 || d->out_oy || d->out_ox) return 0;
+  // two input pointers: thin-Cout only, equal halves of whole 64-channel chunks (the lean SPADE backward: d(gamma) and dout)
+  const bool two = d->C2 != 0;
+  if (two && (d->C2 != d->C1 || d->C1 % 64 || !d->in2 || ((uintptr_t)d->in2 & 15) || d->ld2 % 4 ||
+              (long long)d->N * d->H * d->W * d->ld2 >= (1ll << 30))) return 0;
+  if (d->in_sy != 1 || d->in_sx != 1 || d->out_sy != 1 || d->out_sx != 1 || d->out_oy || d->out_ox) return 0;
   if (d->GH != d->H || d->GW != d->W || d->OH != d->H || d->OW != d->W) return 0;
   if ((long long)d->N * d->H * d->W * d->ld1 >= (1ll << 30)) return 0;          // 32-bit byte offsets
   if (((uintptr_t)d->in1 & 15) || d->ld1 % 4 || ((uintptr_t)d->w & 15) || d->Kp % 4) return 0;
   int tapidx[9];
   if (!window_taps(d, tapidx)) return 0;
-  if (d->C1 == 4 && d->kmode == 1 && d->ldo % 4 == 0 && !((uintptr_t)d->out & 15) &&
+  if (!two && d->C1 == 4 && d->kmode == 1 && d->ldo % 4 == 0 && !((uintptr_t)d->out & 15) &&
       (!d->res || (d->ldr % 4 == 0 && !((uintptr_t)d->res & 15) && (long long)d->N * d->H * d->W * d->ldr < (1ll << 30)))) return 3;
-  if (d->Cout <= 8 && d->C1 >= 64 && d->C1 % 64 == 0 && d->ldo % 2 == 0 && !((uintptr_t)d->out & 7)) return 4;
+  const int Cin = d->C1 + d->C2;
+  if (two) {                                          // a 3x3 window only: the shapes the one-tensor launch of the same conv takes
+    bool window = false;
+    for (int t = 0; t < d->ntaps; ++t) if (d->dy[t] || d->dx[t]) window = true;
+    if (!window) return 0;
+  }
+  if (d->Cout <= 8 && Cin >= 64 && Cin % 64 == 0 && d->ldo % 2 == 0 && !((uintptr_t)d->out & 7)) return 4;
   return 0;
 }
 
@@ -726,7 +828,7 @@ static bool routes_thin32(const ssg_conv_desc* d, int kind) {
 // 128 / 256 -> 6..8 would need 160 - 320 weight registers.
 static int rows_form_mt(const ssg_conv_desc* d, int kind, bool ks1) {
   if (kind != 4 || ks1) return 0;
-  const int kc = d->C1 / 64;
+  const int kc = (d->C1 + d->C2) / 64;
   if (kc != 1 && kc != 2 && kc != 4) return 0;
   const int need = (9 * d->Cout + 15) / 16;
   const int mt = need <= 2 ? 2 : need <= 3 ? 3 : 5;
@@ -742,13 +844,19 @@ int ssg_thin4_conv_id(const ssg_conv_desc* d, int kind) {
   return 9 + kind;
 }
 
-int ssg_thin4_conv_launch(const ssg_conv_desc* d, int kind, hipStream_t st) {
+// mod_dy != nullptr (ssg_thin4_conv_launch_mod; d->res is NULL, the route is thin32_cin or thin4_cin): the launch of `d` whose
+// epilogue adds mod_dy * (1 + mod_g) where a residual would be added.
+static int thin4_launch(const ssg_conv_desc* d, int kind, hipStream_t st, const float* mod_dy, int ldmd, const float* mod_g, int ldmg) {
+  const bool mod = mod_dy != nullptr;
   T4Args a;
   a.in = d->in1; a.w = d->w; a.bias = d->bias; a.res = d->res; a.out = d->out;
-  a.C = d->C1; a.ld = d->ld1; a.N = d->N; a.H = d->H; a.W = d->W; a.Kp = d->Kp; a.kmode = d->kmode;
+  a.C = d->C1 + d->C2; a.ld = d->ld1; a.N = d->N; a.H = d->H; a.W = d->W; a.Kp = d->Kp; a.kmode = d->kmode;
   a.ldr = d->ldr; a.Cout = d->Cout; a.ldo = d->ldo; a.ntaps = d->ntaps;
   a.act = d->act; a.slope = d->slope;
   a.gsave = nullptr; a.ldg = 0;
+  const bool two = d->C2 != 0;                         // kind 4 only (ssg_thin4_conv_kind)
+  a.in2 = two ? d->in2 : nullptr; a.ld2 = two ? d->ld2 : 0;
+  if (mod) { a.res = mod_dy; a.ldr = ldmd; a.gsave = const_cast<float*>(mod_g); a.ldg = ldmg; }
   window_taps(d, a.tapidx);
   a.nt_store = (long long)d->N * d->H * d->W * d->ldo * 4 >= (256ll << 20);
   bool ks1 = true;
@@ -778,7 +886,10 @@ int ssg_thin4_conv_launch(const ssg_conv_desc* d, int kind, hipStream_t st) {
     a.waves_per_group = wpg2;
     const dim3 grid2((unsigned)((wpg2 * a.groups + 3) / 4));
     const bool nt = a.nt_store;
-    if (d->res) {
+    if (mod) {
+      if (nt) hipLaunchKernelGGL((thin32_cin_kernel<3, 1, true>), grid2, block, 0, st, a);
+      else hipLaunchKernelGGL((thin32_cin_kernel<3, 1, false>), grid2, block, 0, st, a);
+    } else if (d->res) {
       if (nt) hipLaunchKernelGGL((thin32_cin_kernel<1, 1, true>), grid2, block, 0, st, a);
       else hipLaunchKernelGGL((thin32_cin_kernel<1, 1, false>), grid2, block, 0, st, a);
     } else {
@@ -795,8 +906,12 @@ int ssg_thin4_conv_launch(const ssg_conv_desc* d, int kind, hipStream_t st) {
     a.ybands = (d->H + a.rh - 1) / a.rh;
     a.total_units = d->N * a.ybands * a.strips;
     const dim3 gridr((unsigned)a.total_units);
-    const int kc = d->C1 / 64;
-    if (mt == 2 && kc == 1) hipLaunchKernelGGL((thin4_cout_kernel_rows<2, 1>), gridr, block, 0, st, a);
+    const int kc = (d->C1 + d->C2) / 64;
+    if (two) {
+      if (mt == 2 && kc == 2) hipLaunchKernelGGL((thin4_cout_kernel_rows<2, 2, true>), gridr, block, 0, st, a);
+      else if (mt == 2) hipLaunchKernelGGL((thin4_cout_kernel_rows<2, 4, true>), gridr, block, 0, st, a);
+      else hipLaunchKernelGGL((thin4_cout_kernel_rows<3, 2, true>), gridr, block, 0, st, a);
+    } else if (mt == 2 && kc == 1) hipLaunchKernelGGL((thin4_cout_kernel_rows<2, 1>), gridr, block, 0, st, a);
     else if (mt == 2 && kc == 2) hipLaunchKernelGGL((thin4_cout_kernel_rows<2, 2>), gridr, block, 0, st, a);
     else if (mt == 2) hipLaunchKernelGGL((thin4_cout_kernel_rows<2, 4>), gridr, block, 0, st, a);
     else if (mt == 3 && kc == 1) hipLaunchKernelGGL((thin4_cout_kernel_rows<3, 1>), gridr, block, 0, st, a);
@@ -806,11 +921,17 @@ int ssg_thin4_conv_launch(const ssg_conv_desc* d, int kind, hipStream_t st) {
     return SSG_OK;
   }
   if (kind == 3) {
-    if (d->res) {
+    if (mod) {
+      if (ks1) hipLaunchKernelGGL((thin4_cin_kernel<1, 1, true, true>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((thin4_cin_kernel<3, 1, true, true>), grid, block, 0, st, a);
+    } else if (d->res) {
       if (ks1) hipLaunchKernelGGL((thin4_cin_kernel<1, 1, true>), grid, block, 0, st, a);
       else hipLaunchKernelGGL((thin4_cin_kernel<3, 1, true>), grid, block, 0, st, a);
     } else if (ks1) hipLaunchKernelGGL((thin4_cin_kernel<1, 2, false>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((thin4_cin_kernel<3, 2, false>), grid, block, 0, st, a);     // two rows in flight (one and four measured equal)
+  } else if (two) {
+    if (d->Cout <= 4) hipLaunchKernelGGL((thin4_cout_kernel<3, 1, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((thin4_cout_kernel<3, 2, true>), grid, block, 0, st, a);
   } else {
     if (d->Cout <= 4) {
       if (ks1) hipLaunchKernelGGL((thin4_cout_kernel<1, 1>), grid, block, 0, st, a);
@@ -822,6 +943,24 @@ int ssg_thin4_conv_launch(const ssg_conv_desc* d, int kind, hipStream_t st) {
   }
   SSG_LAUNCH_CHECK();
   return SSG_OK;
+}
+
+int ssg_thin4_conv_launch(const ssg_conv_desc* d, int kind, hipStream_t st) { return thin4_launch(d, kind, st, nullptr, 0, nullptr, 0); }
+
+// The thin-Cin routes (thin32_cin, thin4_cin) carry the modulated residual; tiny4 (Cout <= 8) and thin-Cout do not.
+int ssg_thin4_conv_mod_ok(const ssg_conv_desc* d, int kind) {
+  return kind == 3 && !routes_tiny(d, kind) && !d->res && !d->bnpart && d->Cout % 4 == 0 &&
+         (long long)d->N * d->H * d->W * d->ldo < (1ll << 30);
+}
+
+int ssg_thin4_conv_launch_mod(const ssg_conv_desc* d, int kind, const float* dy, int lddy, const float* gamma, int ldg, hipStream_t st) {
+  SSG_REQUIRE(ssg_thin4_conv_mod_ok(d, kind), SSG_EINVAL, "spade_dgrad_modulate: not a thin-Cin launch (ssg_spade_dgrad_modulate_ok == 0)");
+  const long long npix = (long long)d->N * d->H * d->W;
+  SSG_REQUIRE(dy && gamma && lddy >= d->Cout && ldg >= d->Cout && lddy % 4 == 0 && ldg % 4 == 0, SSG_EINVAL, "spade_dgrad_modulate: pixel strides");
+  SSG_REQUIRE(ssg_aligned16(dy) && ssg_aligned16(gamma), SSG_EALIGN, "spade_dgrad_modulate: 16-byte alignment");
+  SSG_REQUIRE(npix * lddy < (1ll << 30) && npix * ldg < (1ll << 30), SSG_EINVAL,
+              "spade_dgrad_modulate: tensor beyond 32-bit byte offsets");
+  return thin4_launch(d, kind, st, dy, lddy, gamma, ldg);
 }
 
 // ------------------------------------------------------------------ SPADE: gamma|beta conv + modulation in one kernel
@@ -855,6 +994,7 @@ extern "C" int ssg_spade_conv_modulate_f32(const ssg_conv_desc* d, const float* 
   a.ldr = ldx; a.Cout = d->Cout; a.ldo = d->ldo; a.ntaps = d->ntaps;
   a.act = SSG_ACT_NONE; a.slope = 0.f;
   a.gsave = gamma; a.ldg = ldg;
+  a.in2 = nullptr; a.ld2 = 0;
   window_taps(d, a.tapidx);
   a.nt_store = (long long)d->N * d->H * d->W * C * 4 >= (256ll << 20);
   a.groups = (C + 31) / 32;
