@@ -9,7 +9,7 @@ import torch.nn as nn
 from torch.nn import init
 
 from . import ops
-from .blocks import basic_block, frozen_basic_block
+from .blocks import basic_block, check_block_params, frozen_basic_block
 from .normalization import SPADE
 from ._lib import ACT_NONE, ACT_RELU
 
@@ -43,6 +43,8 @@ class BasicBlock(nn.Module):
         route = self._route()
         if route == 'train':
             return basic_block(x, x2, self.conv1, self.bn1, self.conv2, self.bn2, sc, group=_sync_group(self.bn1))
+        # the eval routes fold parameters with torch ops before any entry sees them: the parameter contract is checked here
+        check_block_params('BasicBlock', x, self.conv1, self.bn1, self.conv2, self.bn2, sc)
         if route == 'frozen':
             # both batch norms on their running statistics with autograd recording (fine-tuning with frozen BN, or any gradient
             # through an eval-mode model): the eval branch's three launches as ONE autograd node, always the fp32-class kernels
@@ -99,7 +101,7 @@ class BasicBlock(nn.Module):
         """((s, mean, invstd) of bn1, the same of bn2) with s = gamma * invstd as _folded() forms it: what the frozen node's
         backward needs to carry gradients through the fold; cached like the folded weights."""
         srcs = (self.bn1.weight, self.bn1.running_mean, self.bn1.running_var, self.bn2.weight, self.bn2.running_mean, self.bn2.running_var)
-        stamp = tuple((t.data_ptr(), t._version) for t in srcs) + (ops._WEIGHT_EPOCH[0], ops._STATS_EPOCH[0])
+        stamp = ops._stamp(srcs, stats=True)
         hit = getattr(self, '_fold_consts_cache', None)
         if hit is not None and hit[0] == stamp:
             return hit[1]
@@ -116,7 +118,7 @@ class BasicBlock(nn.Module):
         cached until a parameter or running statistic changes."""
         srcs = (self.conv1.weight, self.conv2.weight, self.bn1.weight, self.bn1.bias, self.bn1.running_mean, self.bn1.running_var,
                 self.bn2.weight, self.bn2.bias, self.bn2.running_mean, self.bn2.running_var)
-        stamp = tuple((t.data_ptr(), t._version) for t in srcs) + (ops._WEIGHT_EPOCH[0], ops._STATS_EPOCH[0])
+        stamp = ops._stamp(srcs, stats=True)
         hit = getattr(self, '_fold_cache', None)
         if hit is not None and hit[0] == stamp:
             return hit[1]

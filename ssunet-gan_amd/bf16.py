@@ -139,6 +139,7 @@ class _ConvThin(torch.autograd.Function):
 def conv_thin(x, weight, stride=1, pad=0):
     """Dense conv of a <= 4-channel fp32 image into the bf16 family (the EfficientNet stem)."""
     _lib.require_gpu(x)
+    weight = ops.param('bf16.conv_thin', 'weight', weight, x, packed=True)      # (the node reads weight.contiguous())
     return _ConvThin.apply(x, weight, int(stride), pad)
 
 
@@ -148,20 +149,13 @@ def _pack(weight, transpose):
     o, i = weight.shape[0], weight.shape[1]
     rows, cols = (i, o) if transpose else (o, i)
     rows_pad, kp = (rows + 127) // 128 * 128, (cols + 31) // 32 * 32
-    stamp = (weight.data_ptr(), weight._version, ops._WEIGHT_EPOCH[0])
-    cache = weight.__dict__.get('_ssg_pack_bf16')
-    if cache is None or cache[0] != stamp:
-        cache = (stamp, {})
-        try:
-            weight._ssg_pack_bf16 = cache
-        except Exception:
-            pass
-    hit = cache[1].get(transpose)
+    cache = ops._stamped_cache(weight, '_ssg_pack_bf16')
+    hit = cache.get(transpose)
     if hit is None:
         hit = torch.empty((rows_pad, kp), dtype=BF16, device=weight.device)
-        wc = weight.detach().contiguous()
+        wc = ops._dense(weight)
         call('ssg_pack_weights_bf16', ptr(wc), o, i, int(transpose), rows_pad, kp, ptr(hit), stream_ptr())
-        cache[1][transpose] = hit
+        cache[transpose] = hit
     return hit, kp
 
 
@@ -222,7 +216,7 @@ class _Conv1x1(torch.autograd.Function):
 def conv1x1(x, weight):
     """F.conv2d(x, weight) for a [O, I, 1, 1] fp32 parameter on a bf16 tensor (bias-free: model.py:40,56)."""
     _lib.require_gpu(x)
-    return _Conv1x1.apply(x, weight)
+    return _Conv1x1.apply(x, ops.param('bf16.conv1x1', 'weight', weight, x, packed=True))
 
 
 # ----------------------------------------------------------------------------- batch norm (+ swish | + residual)
@@ -307,6 +301,7 @@ def batch_norm_act(x, bn, res=None, act=ACT_NONE):
     _lib.require_gpu(x)
     if act == ACT_SWISH and res is not None:
         raise ValueError('swish with a residual is not a pattern of the MBConv block')
+    bn_w, bn_b, bn_rm, bn_rv = ops.bn_params('bf16.batch_norm_act', bn, x, stats=bn.track_running_stats)
     if bn.training or not bn.track_running_stats:
         if bn.momentum is None:
             raise NotImplementedError('cumulative-average batch norm (momentum=None)')
@@ -314,12 +309,10 @@ def batch_norm_act(x, bn, res=None, act=ACT_NONE):
         if bn.track_running_stats and bn.num_batches_tracked is not None and not ops._synced(group):
             bn.num_batches_tracked.add_(1)           # the reference's synchronised branch never counts batches (batchnorm.py:57-80)
         var_mode = getattr(bn, '_ssg_var_mode', 1 if group is not None else 0)
-        return _BNAct.apply(x, bn.weight, bn.bias, bn.running_mean if bn.track_running_stats else None,
-                            bn.running_var if bn.track_running_stats else None, res, float(bn.eps), float(bn.momentum), int(act),
-                            int(var_mode), group)
+        return _BNAct.apply(x, bn_w, bn_b, bn_rm, bn_rv, res, float(bn.eps), float(bn.momentum), int(act), int(var_mode), group)
     with torch.no_grad():
-        scale = torch.rsqrt(bn.running_var + bn.eps) * bn.weight
-        shift = bn.bias - bn.running_mean * scale
+        scale = torch.rsqrt(bn_rv + bn.eps) * bn_w
+        shift = bn_b - bn_rm * scale
     return _Affine.apply(x, scale.contiguous(), shift.contiguous(), res, int(act))
 
 
@@ -363,6 +356,7 @@ class _DwConv(torch.autograd.Function):
 def dwconv2d(x, weight, stride=1, padding=0):
     _lib.require_gpu(x)
     pad = tuple(int(v) for v in padding) if isinstance(padding, (tuple, list)) else int(padding)
+    weight = ops.param('bf16.dwconv2d', 'weight', weight, x, packed=True)       # (the node reads weight.contiguous())
     return _DwConv.apply(x, weight, int(stride), pad)
 
 

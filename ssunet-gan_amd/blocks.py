@@ -117,16 +117,31 @@ class _BasicBlockFn(torch.autograd.Function):
                 None, None, None, None, None, None, None)
 
 
+def _block_weights(op, x, conv1, conv2, shortcut_conv):
+    """ops.param over the three conv weights of a BasicBlock (read only through ops._pack: they stay the Parameters themselves)."""
+    return (ops.param(op, 'conv1.weight', conv1.weight, x, packed=True), ops.param(op, 'conv2.weight', conv2.weight, x, packed=True),
+            ops.param(op, 'shortcut.weight', shortcut_conv.weight, x, packed=True) if shortcut_conv is not None else None)
+
+
+def check_block_params(op, x, conv1, bn1, conv2, bn2, shortcut_conv):
+    """The parameter contract (ops.param) over everything a BasicBlock holds, for the routes of archs.BasicBlock that fold or
+    compose with torch ops before an entry point of this package sees the operands.  Checks only: returns nothing."""
+    _block_weights(op, x, conv1, conv2, shortcut_conv)
+    for name, bn in (('bn1', bn1), ('bn2', bn2)):
+        ops.bn_params(op, bn, x, stats=bn.track_running_stats, name=name)
+
+
 def basic_block(x1, x2, conv1, bn1, conv2, bn2, shortcut_conv, group=None):
     """Fused training-mode BasicBlock over nn.Conv2d / nn.BatchNorm2d parameter holders."""
+    w1, w2, wsc = _block_weights('basic_block', x1, conv1, conv2, shortcut_conv)
+    g1, b1, rm1, rv1 = ops.bn_params('basic_block', bn1, x1, stats=bn1.track_running_stats, name='bn1')
+    g2, b2, rm2, rv2 = ops.bn_params('basic_block', bn2, x1, stats=bn2.track_running_stats, name='bn2')
     for bn in (bn1, bn2):
         # the reference's synchronised branch never touches num_batches_tracked (batchnorm.py:57-80); its stock branch does
         if bn.track_running_stats and bn.num_batches_tracked is not None and not ops._synced(group):
             bn.num_batches_tracked.add_(1)
     var_mode = getattr(bn1, '_ssg_var_mode', 1 if group is not None else 0)
-    return _BasicBlockFn.apply(x1, x2, conv1.weight, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var,
-                               conv2.weight, bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var,
-                               shortcut_conv.weight if shortcut_conv is not None else None,
+    return _BasicBlockFn.apply(x1, x2, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, wsc,
                                float(bn1.eps), float(bn1.momentum), float(bn2.eps), float(bn2.momentum),
                                int(conv1.stride[0]), var_mode, group)
 
@@ -220,15 +235,17 @@ def frozen_basic_block(x1, x2, conv1, bn1, conv2, bn2, shortcut_conv, folded, co
     """BasicBlock over frozen batch norms as one autograd node.  `folded` = (wf1, bf1, wf2, bf2) and `consts` =
     ((s1, mean1, invstd1), (s2, mean2, invstd2)) come from archs.BasicBlock's caches; nothing here writes a running statistic."""
     wf1, bf1, wf2, bf2 = folded
-    return _FrozenBasicBlockFn.apply(x1, x2, conv1.weight, bn1.weight, bn1.bias, conv2.weight, bn2.weight, bn2.bias,
-                                     shortcut_conv.weight if shortcut_conv is not None else None, wf1, bf1, wf2, bf2,
+    w1, w2, wsc = _block_weights('frozen_basic_block', x1, conv1, conv2, shortcut_conv)
+    g1, b1, _, _ = ops.bn_params('frozen_basic_block', bn1, x1, name='bn1')
+    g2, b2, _, _ = ops.bn_params('frozen_basic_block', bn2, x1, name='bn2')
+    return _FrozenBasicBlockFn.apply(x1, x2, w1, g1, b1, w2, g2, b2, wsc, wf1, bf1, wf2, bf2,
                                      consts[0], consts[1], int(conv1.stride[0]), torch.is_grad_enabled())
 
 
 def _spade_cat(wg, bg, wb, bb):
     """gamma and beta convs as ONE conv nhidden -> 2C: weights / biases concatenated along the output channels.  Cached on
     the gamma weight for one (storage, version, optimizer epoch) of the four tensors, so an eval loop concatenates once."""
-    stamp = tuple((t.data_ptr(), t._version) for t in (wg, bg, wb, bb)) + (ops._WEIGHT_EPOCH[0],)
+    stamp = ops._stamp((wg, bg, wb, bb))
     hit = wg.__dict__.get('_ssg_gb_cat')
     if hit is not None and hit[0] == stamp:
         return hit[1], hit[2]
@@ -429,5 +446,7 @@ class _SpadeFn(torch.autograd.Function):
 
 def spade_self(x, x2map, shared, gamma, beta):
     """Fused SPADE(x, x) over the four nn.Conv2d parameter holders."""
-    return _SpadeFn.apply(x, x2map.weight, x2map.bias, shared.weight, shared.bias, gamma.weight, gamma.bias,
-                          beta.weight, beta.bias, int(x2map.padding[0]))
+    args = []
+    for name, conv in (('x2map', x2map), ('mlp_shared', shared), ('mlp_gamma', gamma), ('mlp_beta', beta)):
+        args += [ops.param('spade_self', name + '.weight', conv.weight, x, packed=True), ops.param('spade_self', name + '.bias', conv.bias, x)]
+    return _SpadeFn.apply(x, *args, int(x2map.padding[0]))

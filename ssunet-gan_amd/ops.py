@@ -102,6 +102,44 @@ def _ld(x):
     return ld
 
 
+# ----------------------------------------------------------------------------- parameter contract
+def param(op, name, t, like=None, written=False, packed=False):
+    """Check the non-activation operand `name` of public entry `op` (a weight, bias, batch-norm affine or running statistic, u / v)
+    before anything is launched, and return what the kernels may read through data_ptr(): fp32, on the device of `like` (the
+    activation; None: any HIP device), dense.  A dense fp32 operand -- every parameter of the training step -- comes back as
+    itself.  A strided one comes back as a dense copy (`.contiguous()`, differentiable: its gradient reaches the original), except
+      * written=True (running statistics, u / v: the kernels write them in place, a copy would swallow the update): ValueError;
+      * packed=True (a weight read only through _pack / bf16._pack, which densify when they pack): the operand itself, so the
+        packs stay stamped on the Parameter and no cache is ever keyed on a temporary.
+    TypeError for another dtype, HipLibraryError for another device: a kernel would misread the one and fault on the other."""
+    if t is None:
+        return None
+    if t.dtype != torch.float32:
+        raise TypeError('%s: %s must be float32 (parameters and statistics are fp32 in every tensor family); got %s' % (op, name, t.dtype))
+    if not t.is_cuda or (like is not None and t.device != like.device):
+        raise _lib.HipLibraryError('%s: %s is on %s; it must be on %s (there is no CPU fallback and no peer access)' % (
+            op, name, t.device, "the input's HIP device" if like is None or not like.is_cuda else like.device))
+    if packed or t.is_contiguous():
+        return t
+    if written:
+        raise ValueError('%s: %s is written in place and must be dense; got shape %s stride %s' % (op, name, tuple(t.shape), t.stride()))
+    return t.contiguous()
+
+
+def bn_params(op, bn, like, stats=True, name='bn'):
+    """param() over the batch-norm module the caller calls `name`: (weight, bias, running_mean, running_var), the statistics
+    None unless `stats`."""
+    rm = bn.running_mean if stats else None
+    rv = bn.running_var if stats else None
+    return (param(op, name + '.weight', bn.weight, like), param(op, name + '.bias', bn.bias, like),
+            param(op, name + '.running_mean', rm, like, written=True), param(op, name + '.running_var', rv, like, written=True))
+
+
+def _dense(t):
+    """`t` as the pack kernels read it: itself when dense, else a detached dense copy (made at pack time only, never cached)."""
+    return t if t.is_contiguous() else t.detach().contiguous()
+
+
 def _ws(nbytes, device):
     return torch.empty((max(int(nbytes), 16) + 15) // 16 * 2, dtype=torch.float64, device=device)
 
@@ -124,11 +162,17 @@ def _attach(t, name, value):
     return value
 
 
+def _stamp(tensors, stats=False):
+    """What every cache of tensors derived from parameters is valid for: the (storage address, autograd version) of each source,
+    the optimizer epoch and, with `stats`, the running-statistics epoch (_STATS_EPOCH).  The one stamp of the package."""
+    return tuple((t.data_ptr(), t._version) for t in tensors) + ((_WEIGHT_EPOCH[0], _STATS_EPOCH[0]) if stats else (_WEIGHT_EPOCH[0],))
+
+
 def _stamped_cache(t, name):
     """The dict kept as attribute `name` ON tensor `t` (never keyed by address alone: a freed tensor's address can be reused by
     another weight), as (stamp, dict).  It is valid for one (storage address, autograd version, optimizer epoch) of `t`: a new
     stamp starts an empty dict."""
-    stamp = (t.data_ptr(), t._version, _WEIGHT_EPOCH[0])
+    stamp = _stamp((t,))
     cache = t.__dict__.get(name)
     if cache is None or cache[0] != stamp:
         cache = _attach(t, name, (stamp, {}))
@@ -159,7 +203,7 @@ def _pack(weight, transpose, taps, cred_pad, c1_for_mode, sigma=None):
     if sigma is not None:
         out = torch.empty((rows, kp), device=weight.device, dtype=torch.float32)
         ky = (C.c_int * nt)(*[t[0] for t in taps]); kx = (C.c_int * nt)(*[t[1] for t in taps])
-        wc = weight.detach().contiguous()
+        wc = _dense(weight)
         call('ssg_pack_weights_scaled_f32', ptr(wc), o, i, kh, kw, int(transpose), nt, ky, kx, kmode, cred_pad, kp, ptr(sigma), ptr(out), stream_ptr())
         return out, kp, kmode
     cache = _stamped_cache(weight, '_ssg_pack')
@@ -170,7 +214,7 @@ def _pack(weight, transpose, taps, cred_pad, c1_for_mode, sigma=None):
     out = torch.empty((rows, kp), device=weight.device, dtype=torch.float32)
     ky = (C.c_int * nt)(*[t[0] for t in taps])
     kx = (C.c_int * nt)(*[t[1] for t in taps])
-    call('ssg_pack_weights_f32', ptr(weight), o, i, kh, kw, int(transpose), nt, ky, kx, kmode, cred_pad, kp, ptr(out), stream_ptr())
+    call('ssg_pack_weights_f32', ptr(_dense(weight)), o, i, kh, kw, int(transpose), nt, ky, kx, kmode, cred_pad, kp, ptr(out), stream_ptr())
     cache[key] = out
     return out, kp, kmode
 
@@ -686,6 +730,8 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, x
     if precision not in _PRECISIONS:
         raise ValueError('conv2d: unknown precision %r (one of %s)' % (precision, ', '.join(_PRECISIONS)))
     _check_wgrad_s2('conv2d', precision, wgrad_s2)
+    weight = param('conv2d', 'weight', weight, x, packed=True)
+    bias = param('conv2d', 'bias', bias, x)
     pad = tuple(int(v) for v in padding) if isinstance(padding, (tuple, list)) else int(padding)
     y, part = _Conv2d.apply(x, x2, weight, bias, int(stride), pad, int(act), float(slope), res, bool(bn_stats), precision, wgrad_s2)
     return (y, part) if bn_stats else y
@@ -825,7 +871,10 @@ def conv2d_bf16x1(x, weight, bias=None, act=ACT_NONE, slope=0.0, x2=None, res=No
     An APPROXIMATION, |error| <= (2^-8 + 2^-18) * conv(|x|, |w|); bias, res and the output are fp32.  Inference only: raises
     RuntimeError when autograd is recording and an argument requires grad, ValueError where `conv2d_bf16x1_ok` says no, and there
     is no CPU fallback."""
-    for t in (x, weight, bias, x2, res):
+    _lib.require_gpu(x)
+    weight = param('conv2d_bf16x1', 'weight', weight, x, packed=True)
+    bias = param('conv2d_bf16x1', 'bias', bias, x)
+    for t in (x2, res):
         if t is not None:
             _lib.require_gpu(t)
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias, x2, res)):
@@ -1072,7 +1121,10 @@ def conv2d_bf16x1_train(x, weight, bias=None, act=ACT_NONE, slope=0.0, x2=None, 
     gradient on the fp32-class kernel, or with wgrad_s2='bf16x1' on wgrad_s2_k32_x1_kernel where its predicate holds.  Raises
     ValueError where `conv2d_bf16x1_ok` / `conv2d_bf16x1_s2_ok` is false or wgrad_s2 is neither 'fp32' nor 'bf16x1'; there is no
     CPU fallback."""
-    for t in (x, weight, bias, x2, res):
+    _lib.require_gpu(x)
+    weight = param('conv2d_bf16x1_train', 'weight', weight, x, packed=True)
+    bias = param('conv2d_bf16x1_train', 'bias', bias, x)
+    for t in (x2, res):
         if t is not None:
             _lib.require_gpu(t)
     _check_wgrad_s2('conv2d_bf16x1_train', 'bf16x1', wgrad_s2)
@@ -1151,7 +1203,8 @@ def _pad_rows(x):
 
 def linear(x, weight, bias=None, act=ACT_NONE, slope=0.0):
     _lib.require_gpu(x)
-    return _Linear.apply(x, weight, bias, int(act), float(slope))
+    # (a strided weight is copied here, not at pack time: the skinny GEMM streams the parameter itself and keeps no pack)
+    return _Linear.apply(x, param('linear', 'weight', weight, x), param('linear', 'bias', bias, x), int(act), float(slope))
 
 
 # ----------------------------------------------------------------------------- batch norm (+residual, +activation)
@@ -1450,6 +1503,7 @@ def batch_norm_act(x, bn, res=None, act=ACT_NONE, slope=0.0, group=None, var_mod
     A `bn` in eval mode (frozen: batchnorm.freeze_batch_norm) normalises with its running estimates, writes none of them, issues
     no collective and is differentiable in x, res, bn.weight and bn.bias."""
     _lib.require_gpu(x)
+    bn_w, bn_b, bn_rm, bn_rv = bn_params('batch_norm_act', bn, x, stats=bn.track_running_stats)
     if bn.training or not bn.track_running_stats:
         if bn.momentum is None:
             raise NotImplementedError('cumulative-average batch norm (momentum=None)')
@@ -1457,29 +1511,28 @@ def batch_norm_act(x, bn, res=None, act=ACT_NONE, slope=0.0, group=None, var_mod
             bn.num_batches_tracked.add_(1)           # the reference's synchronised branch never counts batches (batchnorm.py:57-80)
         if var_mode is None:
             var_mode = getattr(bn, '_ssg_var_mode', 1 if group is not None else 0)
-        return _BatchNormAct.apply(x, bn.weight, bn.bias, bn.running_mean if bn.track_running_stats else None,
-                                   bn.running_var if bn.track_running_stats else None, res, float(bn.eps), float(bn.momentum),
+        return _BatchNormAct.apply(x, bn_w, bn_b, bn_rm, bn_rv, res, float(bn.eps), float(bn.momentum),
                                    int(act), float(slope), int(var_mode), group, stats_part)
     with torch.no_grad():
-        invstd = torch.rsqrt(bn.running_var + bn.eps)
+        invstd = torch.rsqrt(bn_rv + bn.eps)
         scale = invstd
-        if bn.weight is not None:
-            scale = scale * bn.weight
-        shift = -bn.running_mean * scale
-        if bn.bias is not None:
-            shift = shift + bn.bias
+        if bn_w is not None:
+            scale = scale * bn_w
+        shift = -bn_rm * scale
+        if bn_b is not None:
+            shift = shift + bn_b
         c = scale.numel()
-        mean = bn.running_mean
+        mean = bn_rm
         if c % 4:                                           # 1-channel psi batch norm: the padded lanes run with scale = shift = 0
             scale = torch.nn.functional.pad(scale, (0, pad4(c) - c)); shift = torch.nn.functional.pad(shift, (0, pad4(c) - c))
     if c % 4 and torch.is_grad_enabled():                   # only a recorded forward needs the statistics on the padded lanes too
         with torch.no_grad():
             mean = torch.nn.functional.pad(mean, (0, pad4(c) - c)); invstd = torch.nn.functional.pad(invstd, (0, pad4(c) - c))
-    record = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, res, bn.weight, bn.bias))
+    record = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, res, bn_w, bn_b))
     if record and act == ACT_SWISH and res is not None:
         # (the kernel refuses the combination in any forward; said here by name where a graph would be recorded)
         raise NotImplementedError('batch_norm_act: swish with a residual has no backward (its derivative needs the pre-activation sum)')
-    return _AffineAct.apply(x, bn.weight, bn.bias, mean, invstd, scale.contiguous(), shift.contiguous(), res, int(act), float(slope), record)
+    return _AffineAct.apply(x, bn_w, bn_b, mean, invstd, scale.contiguous(), shift.contiguous(), res, int(act), float(slope), record)
 
 
 # ----------------------------------------------------------------------------- pool / unpool / upsample
@@ -1857,6 +1910,8 @@ class _DwConv2d(torch.autograd.Function):
 def dwconv2d(x, weight, bias=None, stride=1, padding=0):
     """Depthwise F.conv2d (groups = C)."""
     _lib.require_gpu(x)
+    weight = param('dwconv2d', 'weight', weight, x, packed=True)      # (the node reads weight.contiguous())
+    bias = param('dwconv2d', 'bias', bias, x)
     pad = tuple(int(v) for v in padding) if isinstance(padding, (tuple, list)) else int(padding)
     return _DwConv2d.apply(x, weight, bias, int(stride), pad)
 
@@ -2252,13 +2307,16 @@ def se_gate(sq, reduce_conv, expand_conv):
     """The squeeze-excite gate for pooled `sq` [N, C, 1, 1] through the block's `_se_reduce` / `_se_expand` 1x1 conv modules;
     None when the shape is outside the fused kernels' range (the caller then runs the convs)."""
     _lib.require_gpu(sq)
-    w1, w2 = reduce_conv.weight, expand_conv.weight
+    w1 = param('se_gate', 'reduce_conv.weight', reduce_conv.weight, sq, packed=True)      # (the node reads dense reshapes of both)
+    w2 = param('se_gate', 'expand_conv.weight', expand_conv.weight, sq, packed=True)
+    b1 = param('se_gate', 'reduce_conv.bias', reduce_conv.bias, sq)
+    b2 = param('se_gate', 'expand_conv.bias', expand_conv.bias, sq)
     n, c = sq.shape[0], sq.shape[1]
     if tuple(w1.shape[1:]) != (c, 1, 1) or tuple(w2.shape) != (c, w1.shape[0], 1, 1) or sq.dtype != torch.float32:
         return None
     if not call('ssg_se_gate_ok', n, c, w1.shape[0]):
         return None
-    return _SEGate.apply(sq, w1, reduce_conv.bias, w2, expand_conv.bias)
+    return _SEGate.apply(sq, w1, b1, w2, b2)
 
 
 class _ChannelScale(torch.autograd.Function):
@@ -2371,13 +2429,19 @@ class _Conv2dSN(torch.autograd.Function):
 def conv2d_sn(x, weight_orig, u, v, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, n_power_iterations=1, eps=1e-12):
     """Spectrally normalised conv2d: see _Conv2dSN.  `n_power_iterations = 0` in eval mode (no update of u, v)."""
     _lib.require_gpu(x)
+    weight_orig = param('conv2d_sn', 'weight_orig', weight_orig, x, packed=True)      # (the node reads weight_orig.contiguous())
+    u = param('conv2d_sn', 'u', u, x, written=True)
+    v = param('conv2d_sn', 'v', v, x, written=True)
+    bias = param('conv2d_sn', 'bias', bias, x)
     pad = tuple(int(p) for p in padding) if isinstance(padding, (tuple, list)) else int(padding)
     return _Conv2dSN.apply(x, weight_orig, u, v, bias, int(stride), pad, int(act), float(slope), int(n_power_iterations), float(eps))
 
 
 def spectral_norm_weight(weight_orig, u, v, n_power_iterations=1, eps=1e-12):
     """weight_orig / sigma after `n_power_iterations` in-place power-iteration updates of u, v."""
-    _lib.require_gpu(weight_orig)
+    weight_orig = param('spectral_norm_weight', 'weight_orig', weight_orig, None, packed=True)      # (the node reads weight_orig.contiguous())
+    u = param('spectral_norm_weight', 'u', u, weight_orig, written=True)
+    v = param('spectral_norm_weight', 'v', v, weight_orig, written=True)
     return _SpectralNormWeight.apply(weight_orig, u, v, int(n_power_iterations), float(eps))
 
 
