@@ -123,7 +123,7 @@ int ssg_conv_set_k32_mode(int mode);
 int64_t ssg_pack_weights_split_bytes(int R, int Kp, int BN);
 int ssg_pack_weights_split_bf16x3(const float* w_packed, int R, int Kp, int BN, void* out, void* stream);
 
-/* Opt-in bf16 INFERENCE convolution (conv_halo_k32_x1.hip): the 3x3 stride-1 pad-1 forward conv of an eval-mode BasicBlock
+/* Opt-in bf16 INFERENCE convolution (conv_halo_k32_bf16.hip): the 3x3 stride-1 pad-1 forward conv of an eval-mode BasicBlock
  * (archs.py:210,212 under model.eval(), api.py:376-390) with both operands rounded ONCE to bf16 (round to nearest even) and one
  * v_mfma_f32_16x16x32_bf16 per product, fp32 accumulation, fp32 tensors in HBM.  An APPROXIMATION: |error| <= (2^-8 + 2^-18) *
  * conv(|x|, |w|) from the operand rounding, plus fp32 accumulation.  Never selected by ssg_conv2d_f32; no mode, no environment
@@ -145,7 +145,7 @@ int ssg_conv2d_bf16x1_f32(const ssg_conv_desc* d, const void* w_bf16x1, void* st
 int64_t ssg_pack_weights_bf16x1_bytes(int R, int Kp, int BN);
 int ssg_pack_weights_bf16x1(const float* w_packed, int R, int Kp, int BN, void* out, void* stream);
 
-/* Opt-in bf16x2 convolution (conv_halo_k32_x2.hip; ops.conv2d(..., precision='bf16x2')): the 3x3 stride-1 pad-1 conv (forward, and
+/* Opt-in bf16x2 convolution (conv_halo_k32_bf16.hip; ops.conv2d(..., precision='bf16x2')): the 3x3 stride-1 pad-1 conv (forward, and
  * the input gradient as the same conv on dout with the transposed pack) with each operand split ONCE into two bf16 terms,
  * x1 = bf16_rne(x), x2 = bf16_rne(x - x1), and three v_mfma_f32_16x16x32_bf16 per product in a fixed order, small terms first:
  * x1 w2, x2 w1, x1 w1 (x2 w2 is dropped).  fp32 accumulation, epilogue and tensors.  An APPROXIMATION: |error| <= (3 * 2^-16 +
@@ -273,7 +273,7 @@ int ssg_conv2d_wgrad_kernel_id(const ssg_wgrad_desc* d);
  * at run time (default on, SSG_WGRAD_K32). */
 int ssg_wgrad_set_k32_mode(int mode);
 
-/* Opt-in bf16x1 weight gradient (conv_wgrad_k32_x1.hip; ops.train_precision('bf16x1')): the contract of ssg_conv2d_wgrad_f32 for the
+/* Opt-in bf16x1 weight gradient (conv_wgrad_k32_bf16.hip; ops.train_precision('bf16x1')): the contract of ssg_conv2d_wgrad_f32 for the
  * 3x3 stride-1 pad-1 conv, with both operands rounded once to bf16 (round to nearest even) and fp32 accumulation -- one MFMA per
  * product instead of six.  An APPROXIMATION: |error| <= (2^-8 + 2^-18) * sum |in| |dout| plus the fp32 accumulation error;
  * ssg_conv2d_wgrad_f32 never routes here.  A workgroup that meets a non-finite accumulator (an fp32 value >= 2^128 - 2^119 rounds
@@ -289,7 +289,7 @@ int64_t ssg_conv2d_wgrad_bf16x1_workspace_bytes(const ssg_wgrad_desc* d);
 int ssg_conv2d_wgrad_bf16x1_f32(const ssg_wgrad_desc* d, void* stream);
 int ssg_conv2d_wgrad_bf16x1_kernel_id(const ssg_wgrad_desc* d);
 
-/* Opt-in bf16x2 weight gradient (conv_wgrad_k32_x2.hip; precision 'bf16x2'): the contract, legal shapes, workspace and ordered
+/* Opt-in bf16x2 weight gradient (conv_wgrad_k32_bf16.hip; precision 'bf16x2'): the contract, legal shapes, workspace and ordered
  * split-K reduction of the bf16x1 group above, with both operands (the x window and dout) split once into two bf16 terms and three
  * MFMAs per product, small terms first: x1 d2, x2 d1, x1 d1.  An APPROXIMATION: |error| <= (3 * 2^-16 + 3 * 2^-32) * sum |in| |dout|
  * plus the fp32 accumulation error; neither ssg_conv2d_wgrad_f32 nor ssg_conv2d_wgrad_bf16x1_f32 routes here.  A workgroup that

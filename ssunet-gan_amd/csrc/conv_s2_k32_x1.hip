@@ -1,11 +1,12 @@
-// One-term bf16 (bf16x1) kernels for the 3x3 STRIDE-2 pad-1 convolution and for its input gradient, the conv_halo_k32_x1.hip
-// contract: fp32 NHWC tensors in HBM, both operands rounded ONCE with (__bf16)v (round to nearest even) on the way into LDS, one
-// v_mfma_f32_16x16x32_bf16 per product, fp32 accumulation, bias / activation / output in fp32, the non-finite guard of conv_slow.h
-// kept.  No bnpart, ws, in_scale, bwd_x, no residual.  An APPROXIMATION, so nothing routes here unless the caller asks
-// (ops.conv2d(..., precision='bf16x1') from the single-conv node).
-// One kernel template, conv_s2_k32_x1_kernel<BN, WAVES_N, NTAPS, S>, the data flow of conv_halo_k32_x1_kernel (weight ring of 3
-// two-step stages fed by LDS-DMA from the one-plane 1128 / 1064 pack; pixel image [k-group][pixel][16 B] per 32-channel chunk,
-// single-buffered, the next chunk's pixels prefetched into registers), with the tap count a template parameter:
+// One-term bf16 (bf16x1) kernels for the 3x3 STRIDE-2 pad-1 convolution and for its input gradient, the one-term contract of
+// conv_halo_k32_bf16.hip: fp32 NHWC tensors in HBM, both operands rounded ONCE with (__bf16)v (round to nearest even) on the way
+// into LDS, one v_mfma_f32_16x16x32_bf16 per product, fp32 accumulation, bias / activation / output in fp32, the non-finite guard
+// of conv_slow.h kept; the tail (recompute and epilogue) is conv_k32_tail.h's, shared with that file.  No bnpart, ws, in_scale,
+// bwd_x, no residual.  An APPROXIMATION, so nothing routes here unless the caller asks (ops.conv2d(..., precision='bf16x1') from
+// the single-conv node).
+// One kernel template, conv_s2_k32_x1_kernel<BN, WAVES_N, NTAPS, S>, the data flow of conv_halo_k32_x1_kernel
+// (weight ring of 3 two-step stages fed by LDS-DMA from the one-plane 1128 / 1064 pack; pixel image [k-group][pixel][16 B] per
+// 32-channel chunk, single-buffered, the next chunk's pixels prefetched into registers), with the tap count a template parameter:
 //   (a) forward, S = 2, NTAPS = 9: tiles of TH x 32 = 4 x 32 outputs; the image is the (2 TH + 1) x 65 = 9 x 65-pixel window.
 //       A tap (ky, kx) of output (py, px) is window pixel (2 py + ky, 2 px + kx): stored row-major that is a 32-byte lane stride,
 //       and the 16 lanes of a ds_read_b128 quarter-wave would span 512 B = twice the 64 banks x 4 B (a two-way conflict on every
@@ -29,7 +30,7 @@
 #include "lds_dma.h"
 #include "conv_args.h"
 #include "mfma_split.h"
-#include "conv_slow.h"
+#include "conv_k32_tail.h"
 
 namespace {
 
@@ -43,7 +44,7 @@ struct Geo {
   static constexpr int HW = (TW - 1) * S + EXT, HH = (TH - 1) * S + EXT, HR = HW * HH;
   static constexpr int PL = (HW + 1) / 2;                  // S = 2: odd-column plane of a row starts here
   static constexpr int NPIX = (HR + 15) / 16 * 16;
-  static constexpr int KGS = NPIX * 16 + 64;               // bytes between k-groups: + 64 B, as conv_halo_k32_x1.hip
+  static constexpr int KGS = NPIX * 16 + 64;               // bytes between k-groups: + 64 B, as conv_halo_k32_bf16.hip
   static constexpr int IMG = (4 * KGS + 1023) / 1024 * 1024;
   static constexpr int lds_bytes(int BN) { return IMG + 3 * 2 * BN * 64; }
   // slot of window pixel (wy, wx) in a k-group's plane
@@ -228,63 +229,10 @@ __global__ __launch_bounds__(4 * WAVES_N * 64, 2) void conv_s2_k32_x1_kernel(con
   wait_vmcnt<0>();
   wait_lds_reads();
 
-  // ---- non-finite operands (conv_slow.h): a workgroup that holds a non-finite accumulator recomputes its tile with fp32 FMAs
-  {
-    bool bad = false;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bad |= ssg_nonfinite(acc[i][j][r]);
-    if (ssg_any_nonfinite(bad)) {
-      float* scr = (float*)lds + tid;                    // value e of this thread at scr[e * NT]; only this thread reads it back
-      const ConvArgs& as = *ssg_reload_args<ConvArgs>();
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int p = wm * WTM + i * 16 + l15;
-#pragma unroll 1
-        for (int e = 0; e < NI * 4; ++e) {
-          const int co = n0 + wn * WTN + (e >> 2) * 16 + kg * 4 + (e & 3);
-          scr[e * NT] = ssg_conv_slow_value<false>(as, n, ty * TH + (p >> 5), tx * TW + (p & 31), co, 0, NTAPS);
-        }
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][j][r] = scr[(j * 4 + r) * NT];
-      }
-    }
-  }
-
-  // ---- epilogue.  acc[i][j][r]: grid pixel p = wm*WTM + i*16 + l15, output channel n0 + wn*64 + j*16 + kg*4 + r; grid pixel
-  // (gy, gx) is output pixel (gy * out_sy + out_oy, gx * out_sx + out_ox).
-  size_t opix[MI]; bool pok[MI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const int p = wm * WTM + i * 16 + l15;
-    const int gy = ty * TH + (p >> 5), gx = tx * TW + (p & 31);
-    pok[i] = gy < a.GH && gx < a.GW;
-    opix[i] = (size_t)(n * a.OH + gy * a.out_sy + a.out_oy) * a.OW + gx * a.out_sx + a.out_ox;
-  }
-#pragma unroll
-  for (int j = 0; j < NI; ++j) {
-    const int co = n0 + wn * WTN + j * 16 + kg * 4;      // Cout % BN == 0: every column is real
-    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-    if (a.bias) bv = *(const f32x4*)(a.bias + co);
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      if (!pok[i]) continue;
-      f32x4 v = acc[i][j] + bv;
-      if (a.act == SSG_ACT_RELU) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = v[r] < 0.f ? 0.f : v[r];
-      } else if (a.act == SSG_ACT_LRELU) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope;
-      }
-      *(f32x4*)(a.out + opix[i] * a.ldo + co) = v;
-    }
-  }
+  // ---- the tail (conv_k32_tail.h): non-finite recompute over the NTAPS taps, then bias / activation / store.  Grid pixel (gy, gx)
+  // is output pixel (gy * out_sy + out_oy, gx * out_sx + out_ox); s2_args refuses a residual and leaves a.res null.
+  ssg_k32_recompute_nonfinite<NTAPS, TH, WTM, WTN, NT>(acc, lds, tid, n, ty, tx, n0, wm, wn, kg, l15);
+  ssg_k32_epilogue<TH, WTM, WTN>(a, acc, n, ty, tx, n0, wm, wn, kg, l15);
 }
 
 // ssg_pack_weights_bf16x1 for any tap count: fp32 packed [R][Kp] (kmode 0 with `ntaps` taps: k = (chunk16 * ntaps + tap) * 16 + c)

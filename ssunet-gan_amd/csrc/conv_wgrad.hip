@@ -381,7 +381,7 @@ extern "C" int ssg_conv2d_wgrad_f32(const ssg_wgrad_desc* d, void* stream) {
   return SSG_OK;
 }
 
-// The ordered second stage alone, for a launcher outside this file (conv_wgrad_k32_x1.hip): `splits` slabs [9 * Cin][Cout] in d->ws
+// The ordered second stage alone, for a launcher outside this file (conv_wgrad_k32_bf16.hip): `splits` slabs [9 * Cin][Cout] in d->ws
 // -> d->dw_oihw, wgrad_reduce_kernel as ssg_conv2d_wgrad_f32 launches it.
 int ssg_wgrad_reduce_launch(const ssg_wgrad_desc* d, int splits, hipStream_t st) {
   RedArgs r;

@@ -35,5 +35,5 @@ bool ssg_wgrad_k32_ok(const ssg_wgrad_desc* d);
 long long ssg_wgrad_k32_steps(const ssg_wgrad_desc* d);
 int ssg_wgrad_k32_launch(const WgArgs& a, dim3 grid, hipStream_t st);
 
-// conv_wgrad.hip: the ordered slab reduce (wgrad_reduce_kernel) for conv_wgrad_k32_x1.hip, which plans and launches on its own
+// conv_wgrad.hip: the ordered slab reduce (wgrad_reduce_kernel) for conv_wgrad_k32_bf16.hip, which plans and launches on its own
 int ssg_wgrad_reduce_launch(const ssg_wgrad_desc* d, int splits, hipStream_t st);

@@ -1,23 +1,36 @@
-// Weight gradient of 3x3 stride-1 pad-1 convolutions, TWO-TERM form on v_mfma_f32_16x16x32_bf16 (opt-in precision 'bf16x2').  The
-// contract of wgrad_k32_x1_kernel (conv_wgrad_k32_x1.hip), whose body this is: dW[tap][ci][co] = sum over pixels of
-// x[p + tap][ci] * dy[p][co], fp32 tensors in HBM, one or two input pointers (concat), split-K slabs [split][tap * Cin + ci][Cout]
-// reduced in order by wgrad_reduce_kernel, OIHW output.  The difference: both operands (the x window and dy) are split ONCE into
-// two bf16 terms on the way into LDS (split2_4 in mfma_split.h: v1 = bf16_rne(v), v2 = bf16_rne(v - v1)), two planes per slot, and
-// a product is three MFMAs in a fixed order, small terms first: x1 * d2, x2 * d1, x1 * d1 (x2 * d2 is dropped):
-// |x d - kept| <= (3 * 2^-16 + 3 * 2^-32) |x d|.  Nothing routes here unless the caller asks (ssg_conv2d_wgrad_bf16x2_f32).
-// Kept from the one-term kernel: the bf16 plane [pixel][64 channels] in 128-byte rows with the chunk XOR keyed by pixel bits 1 and
-// 3, fragments by ds_read_b64_tr_b16, a K-step = 32 pixels of one image row, steps walking DOWN a 32-pixel column strip with the x
-// window rolling through 8 LDS row slots (dy through 4), a barrier interval of TWO image rows whose successors are loaded in two
-// halves, dy as the A operand so that a lane stores 4 consecutive output channels, the tile 9 taps x 64 input channels x 128
-// output channels where Cout % 128 == 0 (NJ = 4) and 9 x 64 x 64 (NJ = 2) elsewhere, the slab plan and the ordered reduction.
-// The three terms of an x row run as three sweeps over its 3 * NJ accumulators, so a dependent MFMA is 3 * NJ issues behind.
-// LDS: x 2 planes x 8 slots x 36 pixels x 128 B = 72 KB, dy 2 planes x 4 slots x (NJ / 2) x 32 x 128 B = 32 / 64 KB: 104 / 136 KB,
-// one 512-thread workgroup per CU.  Registers: 36 / 18 accumulators x 4, 2 x (NJ + 3) fragments x 4, one row of staging values.
+// Weight gradient of 3x3 stride-1 pad-1 convolutions on v_mfma_f32_16x16x32_bf16 with the operands in bf16, ONE body template
+// wgrad_k32_bf16<NJ, TERMS> behind the kernels of the two opt-in precisions: TERMS = 1 is wgrad_k32_x1_kernel<NJ>, 'bf16x1'
+// (ops.train_precision('bf16x1')), TERMS = 2 is wgrad_k32_x2_kernel<NJ>, 'bf16x2'.  The contract of wgrad_k32_kernel (conv_wgrad_k32.hip): dW[tap][ci][co] = sum over pixels of x[p + tap][ci] *
+// dy[p][co], fp32 tensors in HBM, one or two input pointers (concat), split-K slabs [split][tap * Cin + ci][Cout] reduced in order
+// by wgrad_reduce_kernel, OIHW output.  The difference: both operands (the x window and dy) are turned into TERMS bf16 terms ONCE
+// on the way into LDS, one plane per term:
+//   TERMS = 1  (__bf16)v, round to nearest even; one MFMA per product.  An APPROXIMATION (relative operand error 2^-9 each).
+//   TERMS = 2  split2_4 (mfma_split.h): v1 = bf16_rne(v), v2 = bf16_rne(v - v1); a product is three MFMAs in a fixed order, small
+//              terms first: x1 * d2, x2 * d1, x1 * d1 (x2 * d2 is dropped): |x d - kept| <= (3 * 2^-16 + 3 * 2^-32) |x d|.  The
+//              three terms of an x row run as three sweeps over its 3 * NJ accumulators, so a dependent MFMA is 3 * NJ issues
+//              behind.  With the second terms exactly zero the two extra sweeps add zeros: the result is TERMS = 1's.
+// ssg_conv2d_wgrad_f32 and its plan never route here: the caller asks through ssg_conv2d_wgrad_bf16x1_f32 / _bf16x2_f32.
+// What is kept from the split kernel: the bf16 plane [pixel][64 channels] in 128-byte rows with the chunk XOR keyed by pixel bits
+// 1 and 3, fragments by ds_read_b64_tr_b16, a K-step = 32 pixels of one image row, steps walking DOWN a 32-pixel column strip with
+// the x window rolling through LDS row slots, dy as the A operand so that a lane stores 4 consecutive output channels.
+// What is not: with one plane a step is 18 MFMAs per wave on the 9 x 64 x 64 tile, six times the feed rate per MFMA.  So
+//   * a barrier interval covers TWO image rows of the strip (the x window rolls through 8 row slots, two new rows per interval,
+//     dy through 4); the next interval's rows are loaded in two halves, each in flight behind one row's MFMAs;
+//   * the tile is 9 taps x 64 input channels x 128 output channels where Cout % 128 == 0 (NJ = 4: a wave = 16 input channels x
+//     9 taps x 4 output-channel fragments, 36 accumulators, 72 MFMAs and 52 transposed reads per interval and term; a staged x
+//     row serves twice the output channels), and 9 x 64 x 64 (NJ = 2) elsewhere.
+// LDS per term: x 8 slots x 36 pixels x 128 B = 36 KB, dy 4 slots x (NJ / 2) x 32 x 128 B = 16 / 32 KB; 52 / 68 KB for one term,
+// 104 / 136 KB for two, one 512-thread workgroup per CU.  Registers: 36 / 18 accumulators x 4, TERMS x (NJ + 3) fragments x 4, one
+// row of staging values.
 // The summation order is fixed by (slab, K-step, term) and the slabs are reduced in order: it does not depend on the grid
-// beyond the slab plan, which is a function of the shape alone.
-// Legal shapes (ssg_conv2d_wgrad_bf16x2_ok): those of ssg_conv2d_wgrad_bf16x2_ok.
-// Non-finite operands (conv_slow.h): REQUIRED here -- an infinite v1 makes v - v1 a NaN, so every workgroup that reads an infinite
-// or bf16-overflowing operand holds a non-finite accumulator and recomputes its tile from the fp32 operands.
+// beyond the slab plan, which is a function of the shape alone (and the same for both term counts).
+// Legal shapes (ssg_conv2d_wgrad_bf16x1_ok, ssg_conv2d_wgrad_bf16x2_ok: one predicate): the nine row-major taps of the 3x3 window
+// at unit stride over the whole image (GH == H, GW == W), C1 % 64 == C2 % 64 == 0, Cout % 64 == 0, GW >= 17, pixel strides
+// multiples of 4, tensors within 32-bit byte offsets, no in_scale.
+// Non-finite operands (conv_slow.h): an fp32 value >= 2^128 - 2^119 rounds to bf16 infinity although the fp32 product is finite;
+// inf times anything is inf or NaN, so a workgroup that holds a non-finite accumulator recomputes its tile from the fp32 operands.
+// REQUIRED for two terms: an infinite v1 makes v - v1 a NaN, so every workgroup that reads an infinite or bf16-overflowing operand
+// holds a non-finite accumulator.
 #include "common.h"
 #include "lds_dma.h"
 #include "conv_wgrad_args.h"
@@ -41,22 +54,23 @@ constexpr int DSLOTS = 4;
 constexpr int CB = 64;
 constexpr int MAX_ROWS = 128;              // longest accumulation chain of a slab, in K-steps (4096 pixels: wgrad_k32's)
 constexpr int MIN_ROWS = 8;
-constexpr int x2_lds_bytes(int NJ) { return 2 * (XIMG + DSLOTS * (NJ / 2) * DHALF); }      // two planes of each image
+constexpr int lds_bytes_of(int NJ, int TERMS) { return TERMS * (XIMG + DSLOTS * (NJ / 2) * DHALF); }      // one plane of each image per term
 
 // 16-byte chunk c (0..7) of pixel row p sits at chunk position c ^ sw(p)
 __device__ __forceinline__ int sw(int p) { return ((((p >> 1) & 1) | (((p >> 3) & 1) << 1)) << 1); }
 
-template <int NJ>
-__global__ __launch_bounds__(512, 1) void wgrad_k32_x2_kernel(const WgArgs a) {
+template <int NJ, int TERMS>
+__device__ __forceinline__ void wgrad_k32_bf16(const WgArgs a) {
   constexpr int NH = NJ / 2;                             // 64-channel halves of a dy row
   constexpr int BN = 32 * NJ;
   constexpr int DSLOT = NH * DHALF;
+  constexpr int DIMG = DSLOTS * DSLOT;
   static_assert(NJ == 2 || NJ == 4, "64 or 128 output channels per workgroup");
-  static_assert(4 * 512 * 4 <= x2_lds_bytes(NJ), "the slow path's scratch (one accumulator per thread) fits the LDS allocation");
+  static_assert(TERMS == 1 || TERMS == 2, "one rounded term, or the two of split2");
+  static_assert(4 * 512 * 4 <= lds_bytes_of(NJ, TERMS), "the slow path's scratch (one accumulator per thread) fits the LDS allocation");
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
   unsigned char* const ximg = lds;
-  constexpr int DIMG = DSLOTS * DSLOT;
-  unsigned char* const dimg = lds + 2 * XIMG;            // plane 1 of x at ximg + XIMG, of dy at dimg + DIMG
+  unsigned char* const dimg = lds + TERMS * XIMG;        // plane 1 of x at ximg + XIMG, of dy at dimg + DIMG
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -115,11 +129,19 @@ __global__ __launch_bounds__(512, 1) void wgrad_k32_x2_kernel(const WgArgs a) {
     }
     return r;
   };
-  auto put = [&](unsigned char* dst, int plane, u32x4 raw) {      // both terms, `plane` bytes apart
-    bf16x4 p1, p2;
-    split2_4(__builtin_bit_cast(f32x4, raw), p1, p2);    // NaN stays NaN; |v| >= 2^128 - 2^119: p1 = inf, p2 = NaN
-    *(bf16x4*)dst = p1;
-    *(bf16x4*)(dst + plane) = p2;
+  auto put = [&](unsigned char* dst, int plane, u32x4 raw) {      // the terms of four values, `plane` bytes apart
+    const f32x4 v = __builtin_bit_cast(f32x4, raw);
+    if constexpr (TERMS == 1) {
+      bf16x4 p;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) p[e] = (__bf16)v[e];   // round to nearest even; NaN stays NaN, |v| >= 2^128 - 2^119 becomes inf
+      *(bf16x4*)dst = p;
+    } else {
+      bf16x4 p1, p2;
+      split2_4(v, p1, p2);                               // NaN stays NaN; |v| >= 2^128 - 2^119: p1 = inf, p2 = NaN
+      *(bf16x4*)dst = p1;
+      *(bf16x4*)(dst + plane) = p2;
+    }
   };
   auto store_x = [&](const RawX& r, int slot) {
     put(ximg + slot * XSLOT + x_dst, XIMG, r.a);
@@ -203,23 +225,24 @@ __global__ __launch_bounds__(512, 1) void wgrad_k32_x2_kernel(const WgArgs a) {
           const int row = gy + rr;
           if (rr == 0) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1);      // a wave's priority falls as it advances through an interval
           const unsigned char* db = dimg + (row & 3) * DSLOT;
-          bf16x8 df[2][NJ];                              // [plane]
+          bf16x8 df[TERMS][NJ];                          // [plane]
 #pragma unroll
-          for (int h = 0; h < 2; ++h)
+          for (int h = 0; h < TERMS; ++h)
 #pragma unroll
             for (int j = 0; j < NJ; ++j) df[h][j] = frag(db + h * DIMG, doff[j][0], doff[j][1]);
 #pragma unroll
           for (int dyi = 0; dyi < 3; ++dyi) {
             const unsigned char* xb = ximg + ((row + dyi) & 7) * XSLOT;     // x row (row - 1 + dyi) -> slot (x row + 1) & 7
-            bf16x8 xf[2][3];
+            bf16x8 xf[TERMS][3];
 #pragma unroll
-            for (int h = 0; h < 2; ++h)
+            for (int h = 0; h < TERMS; ++h)
 #pragma unroll
               for (int dx = 0; dx < 3; ++dx) xf[h][dx] = frag(xb + h * XIMG, xoff[dx][0], xoff[dx][1]);
-            // A = dy (rows = output channels), B = x (columns = input channels); small terms first: x1 d2, x2 d1, x1 d1
+            // A = dy (rows = output channels), B = x (columns = input channels).  One term: one sweep, x1 d1.  Two terms: three
+            // sweeps, small terms first: x1 d2, x2 d1, x1 d1
 #pragma unroll
-            for (int t = 0; t < 3; ++t) {
-              const int hd = t == 0 ? 1 : 0, hx = t == 1 ? 1 : 0;
+            for (int t = 0; t < 2 * TERMS - 1; ++t) {
+              const int hd = (TERMS == 2 && t == 0) ? 1 : 0, hx = (TERMS == 2 && t == 1) ? 1 : 0;
 #pragma unroll
               for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
@@ -272,10 +295,17 @@ __global__ __launch_bounds__(512, 1) void wgrad_k32_x2_kernel(const WgArgs a) {
       *(f32x4*)(slab + ((size_t)t * Cin + ci) * a.Cout + n0 + (NJ * wn + j) * 16 + 4 * g) = acc[t][j];
 }
 
-struct X2Plan { int nj, mt, nt, splits, steps_per_split; };
+// The two kernels keep the names their profiling labels and traces have had: one line each over the shared body.
+template <int NJ>
+__global__ __launch_bounds__(512, 1) void wgrad_k32_x1_kernel(const WgArgs a) { wgrad_k32_bf16<NJ, 1>(a); }
+template <int NJ>
+__global__ __launch_bounds__(512, 1) void wgrad_k32_x2_kernel(const WgArgs a) { wgrad_k32_bf16<NJ, 2>(a); }
 
-// The shape test alone (no pointers): what ssg_conv2d_wgrad_bf16x2_ok answers.
-bool x2_shape_ok(const ssg_wgrad_desc* d) {
+// ---- host side, the same for both term counts: the shapes, the slab plan and the workspace do not depend on TERMS
+struct Plan { int nj, mt, nt, splits, steps_per_split; };
+
+// The shape test alone (no pointers): what ssg_conv2d_wgrad_bf16x1_ok and ssg_conv2d_wgrad_bf16x2_ok answer.
+bool shape_ok(const ssg_wgrad_desc* d) {
   if (!d || d->in_scale || d->in_shift) return false;
   if (d->ntaps != 9 || d->KH != 3 || d->KW != 3 || d->in_sy != 1 || d->in_sx != 1) return false;
   if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->GH != d->H || d->GW != d->W) return false;
@@ -291,8 +321,8 @@ bool x2_shape_ok(const ssg_wgrad_desc* d) {
 
 // Slabs: a slab is one workgroup's accumulation chain, MIN_ROWS..MAX_ROWS K-steps; within that, the count that leaves the fewest
 // CUs idle in the last wave of 256 workgroups (one workgroup per CU), as wgrad_k32's plan.
-X2Plan x2_plan(const ssg_wgrad_desc* d) {
-  X2Plan p;
+Plan plan(const ssg_wgrad_desc* d) {
+  Plan p;
   p.nj = d->Cout % 128 == 0 ? 4 : 2;
   p.mt = (d->C1 + d->C2) / CB; p.nt = d->Cout / (32 * p.nj);
   const long long steps = (long long)d->N * ((d->GW + KP - 1) / KP) * d->GH;
@@ -312,38 +342,38 @@ X2Plan x2_plan(const ssg_wgrad_desc* d) {
   return p;
 }
 
-int64_t x2_ws_bytes(const ssg_wgrad_desc* d, const X2Plan& p) {
+int64_t ws_bytes(const ssg_wgrad_desc* d, const Plan& p) {
   return (int64_t)p.splits * 9 * (d->C1 + d->C2) * d->Cout * (int64_t)sizeof(float);
 }
 
-template <int NJ>
-int x2_launch(const WgArgs& a, dim3 grid, hipStream_t st) {
-  constexpr int lds_bytes = x2_lds_bytes(NJ);
-  SSG_DYN_LDS_ONCE(wgrad_k32_x2_kernel<NJ>, lds_bytes, "wgrad bf16x2");
-  hipLaunchKernelGGL(wgrad_k32_x2_kernel<NJ>, grid, dim3(512), lds_bytes, st, a);
+int64_t ws_bytes_or_0(const ssg_wgrad_desc* d) { return shape_ok(d) ? ws_bytes(d, plan(d)) : 0; }
+
+template <int NJ, int TERMS>
+int launch(const WgArgs& a, dim3 grid, hipStream_t st) {
+  constexpr int lds_bytes = lds_bytes_of(NJ, TERMS);
+  if constexpr (TERMS == 1) {
+    SSG_DYN_LDS_ONCE(wgrad_k32_x1_kernel<NJ>, lds_bytes, "wgrad bf16x1");
+    hipLaunchKernelGGL(wgrad_k32_x1_kernel<NJ>, grid, dim3(512), lds_bytes, st, a);
+  } else {
+    SSG_DYN_LDS_ONCE(wgrad_k32_x2_kernel<NJ>, lds_bytes, "wgrad bf16x2");
+    hipLaunchKernelGGL(wgrad_k32_x2_kernel<NJ>, grid, dim3(512), lds_bytes, st, a);
+  }
   SSG_LAUNCH_CHECK();
   return SSG_OK;
 }
 
-}  // namespace
-
-extern "C" int ssg_conv2d_wgrad_bf16x2_ok(const ssg_wgrad_desc* d) { return x2_shape_ok(d) ? 1 : 0; }
-
-extern "C" int ssg_conv2d_wgrad_bf16x2_kernel_id(const ssg_wgrad_desc* d) { return x2_shape_ok(d) ? 92 : SSG_EINVAL; }
-
-extern "C" int64_t ssg_conv2d_wgrad_bf16x2_workspace_bytes(const ssg_wgrad_desc* d) {
-  return x2_shape_ok(d) ? x2_ws_bytes(d, x2_plan(d)) : 0;
-}
-
-extern "C" int ssg_conv2d_wgrad_bf16x2_f32(const ssg_wgrad_desc* d, void* stream) {
-  SSG_REQUIRE(d && d->in1 && d->dout && d->dw_oihw && d->ws, SSG_EINVAL, "wgrad bf16x2: null pointer");
-  SSG_REQUIRE(d->C2 == 0 || d->in2, SSG_EINVAL, "wgrad bf16x2: C2 > 0 needs in2");
-  SSG_REQUIRE(x2_shape_ok(d), SSG_EINVAL,
-              "wgrad bf16x2: not the 3x3 stride-1 pad-1 weight gradient with C1 %% 64 == C2 %% 64 == Cout %% 64 == 0, GW >= 17, 32-bit byte offsets "
-              "and no in_scale (C1=%d C2=%d Cout=%d GW=%d ntaps=%d stride=%d)", d->C1, d->C2, d->Cout, d->GW, d->ntaps, d->in_sy);
-  SSG_REQUIRE(ssg_aligned16(d->in1) && ssg_aligned16(d->in2) && ssg_aligned16(d->dout) && ssg_aligned16(d->ws), SSG_EALIGN, "wgrad bf16x2: alignment");
-  const X2Plan p = x2_plan(d);
-  SSG_REQUIRE(d->ws_bytes >= x2_ws_bytes(d, p), SSG_EINVAL, "wgrad bf16x2: workspace too small");
+// Validate, launch the slabs, reduce them in order.  `fam`: the precision's name in the messages.
+template <int TERMS>
+int run(const ssg_wgrad_desc* d, void* stream) {
+  const char* fam = TERMS == 1 ? "bf16x1" : "bf16x2";
+  SSG_REQUIRE(d && d->in1 && d->dout && d->dw_oihw && d->ws, SSG_EINVAL, "wgrad %s: null pointer", fam);
+  SSG_REQUIRE(d->C2 == 0 || d->in2, SSG_EINVAL, "wgrad %s: C2 > 0 needs in2", fam);
+  SSG_REQUIRE(shape_ok(d), SSG_EINVAL,
+              "wgrad %s: not the 3x3 stride-1 pad-1 weight gradient with C1 %% 64 == C2 %% 64 == Cout %% 64 == 0, GW >= 17, 32-bit byte offsets "
+              "and no in_scale (C1=%d C2=%d Cout=%d GW=%d ntaps=%d stride=%d)", fam, d->C1, d->C2, d->Cout, d->GW, d->ntaps, d->in_sy);
+  SSG_REQUIRE(ssg_aligned16(d->in1) && ssg_aligned16(d->in2) && ssg_aligned16(d->dout) && ssg_aligned16(d->ws), SSG_EALIGN, "wgrad %s: alignment", fam);
+  const Plan p = plan(d);
+  SSG_REQUIRE(d->ws_bytes >= ws_bytes(d, p), SSG_EINVAL, "wgrad %s: workspace too small", fam);
   hipStream_t st = (hipStream_t)stream;
   WgArgs a{};
   a.in1 = d->in1; a.in2 = d->C2 ? d->in2 : d->in1; a.dout = d->dout; a.ws = d->ws;
@@ -355,7 +385,19 @@ extern "C" int ssg_conv2d_wgrad_bf16x2_f32(const ssg_wgrad_desc* d, void* stream
   a.Ptot = (long long)d->N * d->GH * d->GW;
   a.steps_per_split = p.steps_per_split;
   const dim3 grid((unsigned)p.mt, (unsigned)p.nt, (unsigned)p.splits);
-  const int rc = p.nj == 4 ? x2_launch<4>(a, grid, st) : x2_launch<2>(a, grid, st);
+  const int rc = p.nj == 4 ? launch<4, TERMS>(a, grid, st) : launch<2, TERMS>(a, grid, st);
   if (rc != SSG_OK) return rc;
   return ssg_wgrad_reduce_launch(d, p.splits, st);
 }
+
+}  // namespace
+
+extern "C" int ssg_conv2d_wgrad_bf16x1_ok(const ssg_wgrad_desc* d) { return shape_ok(d) ? 1 : 0; }
+extern "C" int ssg_conv2d_wgrad_bf16x1_kernel_id(const ssg_wgrad_desc* d) { return shape_ok(d) ? 72 : SSG_EINVAL; }
+extern "C" int64_t ssg_conv2d_wgrad_bf16x1_workspace_bytes(const ssg_wgrad_desc* d) { return ws_bytes_or_0(d); }
+extern "C" int ssg_conv2d_wgrad_bf16x1_f32(const ssg_wgrad_desc* d, void* stream) { return run<1>(d, stream); }
+
+extern "C" int ssg_conv2d_wgrad_bf16x2_ok(const ssg_wgrad_desc* d) { return shape_ok(d) ? 1 : 0; }
+extern "C" int ssg_conv2d_wgrad_bf16x2_kernel_id(const ssg_wgrad_desc* d) { return shape_ok(d) ? 92 : SSG_EINVAL; }
+extern "C" int64_t ssg_conv2d_wgrad_bf16x2_workspace_bytes(const ssg_wgrad_desc* d) { return ws_bytes_or_0(d); }
+extern "C" int ssg_conv2d_wgrad_bf16x2_f32(const ssg_wgrad_desc* d, void* stream) { return run<2>(d, stream); }

@@ -1,6 +1,6 @@
 // Weight gradient of 3x3 STRIDE-2 pad-1 convolutions, ONE-TERM form on v_mfma_f32_16x16x32_bf16 (opt-in: precision 'bf16x1' with
 // wgrad_s2 'bf16x1').  dW[ky][kx][ci][co] = sum over n, oy, ox of x[n, 2oy + ky - 1, 2ox + kx - 1, ci] * dy[n, oy, ox, co].
-// The contract and data flow of wgrad_k32_x1_kernel (conv_wgrad_k32_x1.hip): fp32 NHWC tensors in HBM, both operands rounded ONCE
+// The contract and data flow of wgrad_k32_x1_kernel (conv_wgrad_k32_bf16.hip): fp32 NHWC tensors in HBM, both operands rounded ONCE
 // to bf16 on the way into LDS ((__bf16)v, round to nearest even), one MFMA per product with fp32 accumulation, dy as the A operand,
 // fragments by ds_read_b64_tr_b16 from [pixel][64 channels] planes of 128-byte rows with the chunk XOR keyed by pixel bits 1 and 3,
 // split-K slabs [split][tap * Cin + ci][Cout] reduced in order by wgrad_reduce_kernel, OIHW output, the non-finite guard of
@@ -279,7 +279,7 @@ bool s2_shape_ok(const ssg_wgrad_desc* d) {
   return xb <= 0xfffffff0ull && db <= 0xfffffff0ull;
 }
 
-// Slabs: x1_plan's rule (conv_wgrad_k32_x1.hip) on steps = N * ceil(GW / 32) * GH -- a slab is one workgroup's accumulation chain,
+// Slabs: the rule of plan() in conv_wgrad_k32_bf16.hip on steps = N * ceil(GW / 32) * GH -- a slab is one workgroup's accumulation chain,
 // MIN_ROWS..MAX_ROWS K-steps; within that, the count that leaves the fewest CUs idle in the last wave of 256 workgroups.
 S2Plan s2_plan(const ssg_wgrad_desc* d) {
   S2Plan p;

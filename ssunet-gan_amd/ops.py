@@ -506,7 +506,7 @@ def _conv_fwd_impl(x1, x2, weight, bias, stride, pad, act, slope, res=None, out=
     _conv_bf16x1_impl where conv2d_bf16x1_ok holds (part is then None: that launcher has no statistics epilogue) and on the
     fp32-class kernel below where it refuses.  x1_s2 (the single-conv node only): a 3x3 stride-2 pad-1 conv without x2 / res asks
     _conv_s2_bf16x1_impl first in the same way.  precision='bf16x2': the same routing to the two-term kernel
-    (csrc/conv_halo_k32_x2.hip) for the unit-stride conv; stride 2 stays fp32-class."""
+    (csrc/conv_halo_k32_bf16.hip) for the unit-stride conv; stride 2 stays fp32-class."""
     if _x1_routed(precision, stride, pad, wscale, in_affine) and conv2d_bf16x1_ok(x1, weight, x2=x2, res=res, family=precision):
         y = _conv_bf16x1_impl(x1, weight, bias, act, slope, x2=x2, res=res, out=out, family=precision)
         return (y, None) if want_bn else y
@@ -738,14 +738,14 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, x
 
 
 # ----------------------------------------------------------------------------- opt-in bf16 inference convolution
-# csrc/conv_halo_k32_x1.hip: the 3x3 stride-1 pad-1 forward conv with both operands rounded once to bf16 and one MFMA per product
+# csrc/conv_halo_k32_bf16.hip: the 3x3 stride-1 pad-1 forward conv with both operands rounded once to bf16 and one MFMA per product
 # (ssg_conv2d_bf16x1_f32).  An approximation, forward only, chosen per call: nothing here is reached from a training path, and
 # ops.conv2d never routes to it.
 _X1_LABELS = {70: 'conv_halo_k32_x1_kernel<128>', 71: 'conv_halo_k32_x1_kernel<64>'}
 _X1_KIND = (_X1_LABELS, 'ssg_conv2d_bf16x1_kernel_id', _CONV_SHAPE)
 _X1_TAPS = _taps_fwd(3, 3, 1)
 _PRECISIONS = ('fp32', 'bf16x1', 'bf16x2')
-# csrc/conv_halo_k32_x2.hip / conv_wgrad_k32_x2.hip: the two-term kernels behind precision='bf16x2', same descriptors and call
+# csrc/conv_halo_k32_bf16.hip / conv_wgrad_k32_bf16.hip: the two-term kernels behind precision='bf16x2', same descriptors and call
 # shapes as the one-term ones.  A family = the entry-point infix, its label tables and the cache attribute of its weight packs.
 _X2_LABELS = {90: 'conv_halo_k32_x2_kernel<128>', 91: 'conv_halo_k32_x2_kernel<64>'}
 _X2_KIND = (_X2_LABELS, 'ssg_conv2d_bf16x2_kernel_id', _CONV_SHAPE)
@@ -888,7 +888,7 @@ def conv2d_bf16x1(x, weight, bias=None, act=ACT_NONE, slope=0.0, x2=None, res=No
 # ----------------------------------------------------------------------------- opt-in bf16x1 training
 # 'fp32 master weights, bf16 operands, fp32 accumulation' for the dense 3x3 stride-1 convs: forward and input gradient on
 # conv_halo_k32_x1_kernel (the input gradient is the same convolution on dy with the transposed pack and the taps (1 - ky, 1 - kx)),
-# weight gradient on wgrad_k32_x1_kernel (csrc/conv_wgrad_k32_x1.hip).  Every tensor in HBM stays fp32.  Chosen by the caller:
+# weight gradient on wgrad_k32_x1_kernel (csrc/conv_wgrad_k32_bf16.hip).  Every tensor in HBM stays fp32.  Chosen by the caller:
 # ops.conv2d never comes here.
 _WGRAD_X1_LABELS = {72: 'wgrad_k32_x1_kernel'}
 _WGRAD_X1_KIND = (_WGRAD_X1_LABELS, 'ssg_conv2d_wgrad_bf16x1_kernel_id', _WGRAD_SHAPE)

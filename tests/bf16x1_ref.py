@@ -1,4 +1,4 @@
-"""Reference arithmetic for the opt-in bf16 inference convolution (csrc/conv_halo_k32_x1.hip, ops.conv2d_bf16x1): plain torch on
+"""Reference arithmetic for the opt-in bf16 inference convolution (csrc/conv_halo_k32_bf16.hip, ops.conv2d_bf16x1): plain torch on
 the CPU, fp64.  Plain helper module (not a conftest), shared by tests/test_bf16x1_ref.py (CPU rehearsal of the gates) and the two
 GPU files.  The kernel rounds x, x2 and the weights ONCE to bf16 (round to nearest even) and accumulates exact products in fp32;
 bias, residual and activation are fp32."""

@@ -1,4 +1,4 @@
-"""Reference arithmetic for the opt-in two-term precision 'bf16x2' (csrc/conv_halo_k32_x2.hip, csrc/conv_wgrad_k32_x2.hip): plain
+"""Reference arithmetic for the opt-in two-term precision 'bf16x2' (csrc/conv_halo_k32_bf16.hip, csrc/conv_wgrad_k32_bf16.hip): plain
 torch / numpy on the CPU, fp64.  Plain helper module (not a conftest), shared by tests/test_bf16x2_ref.py (CPU rehearsal of the
 gates) and the three GPU files.
 

@@ -1,4 +1,4 @@
-"""CPU: the host side of the bf16x1 inference convolution (csrc/conv_halo_k32_x1.hip) -- exported symbols, host validation before
+"""CPU: the host side of the bf16x1 inference convolution (csrc/conv_halo_k32_bf16.hip) -- exported symbols, host validation before
 any launch, the legality predicate on descriptors, the pack size.  No GPU, no launches."""
 import ctypes
 

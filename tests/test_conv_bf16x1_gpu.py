@@ -1,4 +1,4 @@
-"""ops.conv2d_bf16x1 (csrc/conv_halo_k32_x1.hip): the opt-in one-term bf16 3x3 convolution for inference.  Gates, per case of
+"""ops.conv2d_bf16x1 (csrc/conv_halo_k32_bf16.hip): the opt-in one-term bf16 3x3 convolution for inference.  Gates, per case of
 tests/bf16x1_ref.py (rehearsed on the CPU in tests/test_bf16x1_ref.py):
   (a) route     the launch is labelled halo_k32_x1; over the file, every tile shape the build instantiates has run;
   (b) accuracy  against the fp64 conv of the bf16-rounded operands: max error <= 2 x that of the fp32-MFMA kernel

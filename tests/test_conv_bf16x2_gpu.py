@@ -1,4 +1,4 @@
-"""ssg_conv2d_bf16x2_f32 / ssg_pack_weights_bf16x2 (csrc/conv_halo_k32_x2.hip, kernel ids 90 / 91) through the C-ABI: the two-term
+"""ssg_conv2d_bf16x2_f32 / ssg_pack_weights_bf16x2 (csrc/conv_halo_k32_bf16.hip, kernel ids 90 / 91) through the C-ABI: the two-term
 3x3 stride-1 pad-1 convolution, forward and input gradient, against tests/bf16x2_ref.py (rehearsed in tests/test_bf16x2_ref.py).
 
 Per case, with bias + residual + activation in the epilogue and every pixel stride wider than its channels (operands and the
@@ -29,19 +29,20 @@ def _g(seed):
     return torch.Generator().manual_seed(seed)
 
 
-def _launch_fwd(pkg, x1, x2, wd, bias, res, out, code, slope):
-    """One ssg_conv2d_bf16x2_f32 launch as ops._conv_bf16x1_impl builds it, with the route asserted; returns the kernel id."""
+def _launch_fwd(pkg, x1, x2, wd, bias, res, out, code, slope, family='bf16x2'):
+    """One ssg_conv2d_bf16x2_f32 launch as ops._conv_bf16x1_impl builds it, with the route asserted; returns the kernel id.
+    family='bf16x1': the one-term entry points on the same descriptor (format codes 1128 / 1064)."""
     ops, lib = pkg.ops, pkg._lib
     d = ops._x1_desc(x1, x2, wd, res, out)
     wpk, kp, kmode = ops._pack(wd, 0, ops._X1_TAPS, wd.shape[1], x1.shape[1])
     d.w = wpk.data_ptr(); d.Kp = kp; d.kmode = kmode
     d.bias = bias.data_ptr() if bias is not None else None
     d.act = code; d.slope = slope
-    fmt = lib.call('ssg_conv2d_bf16x2_ok', C.byref(d))
-    assert fmt == (2128 if wd.shape[0] % 128 == 0 else 2064), fmt
-    kid = lib.call('ssg_conv2d_bf16x2_kernel_id', C.byref(d))
-    pack = ops._x1_pack(wd, wpk, kp, fmt, family='bf16x2')
-    lib.call('ssg_conv2d_bf16x2_f32', C.byref(d), ops.ptr(pack), ops.stream_ptr())
+    fmt = lib.call('ssg_conv2d_%s_ok' % family, C.byref(d))
+    assert fmt == (2000 if family == 'bf16x2' else 1000) + (128 if wd.shape[0] % 128 == 0 else 64), fmt
+    kid = lib.call('ssg_conv2d_%s_kernel_id' % family, C.byref(d))
+    pack = ops._x1_pack(wd, wpk, kp, fmt, family=family)
+    lib.call('ssg_conv2d_%s_f32' % family, C.byref(d), ops.ptr(pack), ops.stream_ptr())
     return kid
 
 
@@ -116,6 +117,34 @@ def test_forward(pkg, dev, name, kind):
     LP.check_slice(out, written=True)
     e = 2 + (1 if act == 'lrelu' else 0)
     _judge('fwd %s %s' % (name, kind), out.cpu().double(), x, wt, bias, res, act, slope, exact_class, K, e)
+
+
+@pytest.mark.parametrize('co', [64, 128])
+def test_bf16_operands_give_the_one_term_kernels_result(pkg, dev, co):
+    """The two-term kernel is the one-term kernel plus two sweeps of small terms.  With every operand a bf16 value, split2's second
+    term x - bf16(x) is exactly zero, the sweeps x1 w2 and x2 w1 add zeros, and the one-term and two-term kernels return EQUAL
+    values (compared as floats: an accumulator of -0 may come back +0).  No reference is involved.  One image of 9 x 33 pixels
+    (a tile edge crossed both ways), two 32-channel chunks through the concat, bias + residual + LeakyReLU in the shared epilogue,
+    BN = 64 and BN = 128."""
+    n, c1, c2, h, w = 1, 32, 32, 9, 33
+    K = 9 * (c1 + c2)
+    g = _g(450 + co)
+    x, wt = R.rb(R.normal((n, c1 + c2, h, w), g)), R.rb(R.normal((co, c1 + c2, 3, 3), g, K ** -0.5))
+    bias, res = R.normal((co,), g), R.normal((n, co, h, w), g)
+    xs1 = LP.poisoned_slice(x[:, :c1].contiguous(), c1 + 32, 16, dev)
+    xs2 = LP.poisoned_slice(x[:, c1:].contiguous(), c2 + 16, 8, dev)
+    rs = LP.poisoned_slice(res, co + 16, 8, dev)
+    got = {}
+    for family, ids in (('bf16x1', (70, 71)), ('bf16x2', (90, 91))):
+        out = LP.canary_slice(n, co, h, w, co + 8, 4, dev)
+        kid = _launch_fwd(pkg, xs1, xs2, wt.to(dev), bias.to(dev), rs, out, 2, 0.25, family)
+        assert kid == ids[0 if co % 128 == 0 else 1]
+        for t in (xs1, xs2, rs):
+            LP.check_slice(t)
+        LP.check_slice(out, written=True)
+        got[family] = out.cpu()
+    assert bool(torch.isfinite(got['bf16x1']).all().item()) and bool((got['bf16x1'] < 0).any().item())
+    assert torch.equal(got['bf16x1'], got['bf16x2'])
 
 
 @pytest.mark.parametrize('kind', ['ints', 'x12', 'w12', 'normal'])

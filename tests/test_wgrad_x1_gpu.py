@@ -1,4 +1,4 @@
-"""ssg_conv2d_wgrad_bf16x1_f32 (csrc/conv_wgrad_k32_x1.hip, kernel id 72) against tests/wgrad_x1_ref.py, through the C-ABI.
+"""ssg_conv2d_wgrad_bf16x1_f32 (csrc/conv_wgrad_k32_bf16.hip, kernel id 72) against tests/wgrad_x1_ref.py, through the C-ABI.
 tests/test_wgrad_x1_ref.py rehearses the gates on the CPU: the float32 emulation passes them at these cases, each planted defect
 fails one.
 

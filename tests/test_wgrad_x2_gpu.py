@@ -1,4 +1,4 @@
-"""ssg_conv2d_wgrad_bf16x2_f32 (csrc/conv_wgrad_k32_x2.hip, kernel id 92) through the C-ABI: the two-term weight gradient of the
+"""ssg_conv2d_wgrad_bf16x2_f32 (csrc/conv_wgrad_k32_bf16.hip, kernel id 92) through the C-ABI: the two-term weight gradient of the
 3x3 stride-1 pad-1 conv against tests/bf16x2_ref.py (rehearsed in tests/test_bf16x2_ref.py).
 
 Per case (N H W <= 2000, every pixel stride wider than its channels, dw and the workspace NaN-filled, two runs with the same bits):
@@ -99,6 +99,24 @@ def test_weight_gradient(pkg, dev, name, kind):
     print('RATIO wgrad %s P=%d: |got - quantised| / gate max %.4f; |got - exact| / (gate + bound) max %.4f; |got - exact| / bound max %.4f'
           % (name, P, rq, re, ((dw - exact).abs() / (R.BOUND * mag)).max().item()))
     assert rq <= 1 and re <= 1, (rq, re)
+
+
+@pytest.mark.parametrize('name', ['two_ptr_o192_9x33', 'c64_o128_17x40'], ids=['nj2_concat', 'nj4'])
+def test_bf16_operands_give_the_one_term_kernels_result(pkg, dev, name):
+    """The two-term kernel is the one-term kernel plus two sweeps of small terms.  With N(0, 1) operands rounded to bf16 and back,
+    split2's second term v - bf16(v) is exactly zero, the sweeps x1 d2 and x2 d1 add zeros, and ssg_conv2d_wgrad_bf16x1 and
+    ..._bf16x2 on the same descriptor and buffers (one plan, one workspace size) return EQUAL values (compared as floats: an
+    accumulator of -0 may come back +0).  No reference is involved.  NJ = 2 (Cout 192, through the concat) and NJ = 4 (Cout 128)."""
+    n, c1, c2, co, h, w = R.WGRAD_CASES[name]
+    g = _g(800 + len(name))
+    x, d = R.rb(R.normal((n, c1 + c2, h, w), g)), R.rb(R.normal((n, co, h, w), g))
+    L = _x2_launch(pkg, dev, x, c1, d)
+    dw2 = L.run()
+    L.entry = 'ssg_conv2d_wgrad_bf16x1'
+    assert pkg._lib.call('ssg_conv2d_wgrad_bf16x1_kernel_id', C.byref(L.d)) == 72
+    dw1 = L.run()
+    assert bool(torch.isfinite(dw1).all().item()) and bool((dw1 != 0).any().item())
+    assert torch.equal(dw1, dw2)
 
 
 @pytest.mark.parametrize('side', ['x', 'dout'])

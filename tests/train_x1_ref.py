@@ -1,5 +1,5 @@
 """A quantised fp64 BasicBlock, train mode and frozen, in plain torch on the CPU: the reference for ops.train_precision('bf16x1')
-(blocks._BasicBlockFn / _FrozenBasicBlockFn on csrc/conv_halo_k32_x1.hip and csrc/conv_wgrad_k32_x1.hip).  Plain helper module
+(blocks._BasicBlockFn / _FrozenBasicBlockFn on csrc/conv_halo_k32_bf16.hip and csrc/conv_wgrad_k32_bf16.hip).  Plain helper module
 (not a conftest); nothing here calls an op under test.
 
 The block rounds to bf16 (bn_ref.bf16_rne) exactly where the kernels do, and nowhere else:

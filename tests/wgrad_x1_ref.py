@@ -1,4 +1,4 @@
-"""Reference for the opt-in bf16x1 weight gradient (csrc/conv_wgrad_k32_x1.hip, ssg_conv2d_wgrad_bf16x1_f32).  Plain helper
+"""Reference for the opt-in bf16x1 weight gradient (csrc/conv_wgrad_k32_bf16.hip, ssg_conv2d_wgrad_bf16x1_f32).  Plain helper
 module (not a conftest), numpy only, built on wgrad_ref: nothing here calls an op under test.
 
 The kernel rounds x and dout ONCE to bf16 (round to nearest even) on the way into LDS and accumulates in fp32.  A product of two
@@ -52,7 +52,7 @@ def case(name):
 
 
 def plan(c):
-    """x1_plan of conv_wgrad_k32_x1.hip restated: (nj, mt, nt, steps, steps_per_split, splits)."""
+    """plan() of conv_wgrad_k32_bf16.hip restated: (nj, mt, nt, steps, steps_per_split, splits)."""
     g = wr.geom(c)
     nj = 4 if c.Cout % 128 == 0 else 2
     mt, nt = g.Cin // 64, c.Cout // (32 * nj)

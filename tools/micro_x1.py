@@ -1,4 +1,4 @@
-"""The one-term bf16 inference conv (conv_halo_k32_x1.hip, ops.conv2d_bf16x1) against the fp32-class kernel ops.conv2d launches for
+"""The one-term bf16 inference conv (conv_halo_k32_bf16.hip, ops.conv2d_bf16x1) against the fp32-class kernel ops.conv2d launches for
 the same tensors, per layer: the 3x3 stride-1 shapes of UNet_R_SS_v2's eval forward at 512^2, batch 9 and 12 (what segment_image
 runs with and without dedupe).  HIP events, both kernels in the same process, alternated over three rounds, best round each,
 random operands, bias + ReLU epilogue as in the folded BasicBlock.  One line per (shape, batch); `route` says whether the new
