@@ -463,6 +463,34 @@ int ssg_bn_bwd_apply_f32(const float* x, const float* y, const float* dy, int64_
                          const double* sums, double count, int act, float slope,
                          float* dx, int lddx, float* dres, int lddres,
                          float* dweight, float* dbias, void* stream);
+/* 1-bit activation masks.  Where the forward had a residual, the backward needs of y only the sign: ssg_bn_apply_mask_f32 is
+ * ssg_bn_apply_f32 (same y, bit for bit) that also writes mask[p][c / 8] bit c % 8 = (y[p][c] > 0), tested on the stored value
+ * (uint8, row stride ldm >= C / 8 bytes), and the _mask forms of the two backward passes read those bytes where the plain ones
+ * read y: 1/32 of the bytes, the same sums, dx, dres, dweight and dbias bit for bit.
+ * ssg_bn_mask_ok(C, act): 1 where the forms apply -- C % 8 == 0 and act ReLU or LeakyReLU (fp32 tensors only); they return
+ * SSG_EINVAL for anything else. */
+int ssg_bn_mask_ok(int C, int act);
+int ssg_bn_apply_mask_f32(const float* x, int64_t P, int C, int ld, const float* scale, const float* shift,
+                          const float* res, int ldr, int act, float slope, float* y, int ldy,
+                          uint8_t* mask, int ldm, void* stream);
+int ssg_bn_bwd_reduce_mask_f32(const float* x, const uint8_t* mask, const float* dy, int64_t P, int C,
+                               int ldx, int ldm, int lddy, const float* mean, const float* invstd,
+                               int act, float slope, double* sums, int with_count, void* ws, void* stream);
+int ssg_bn_bwd_apply_mask_f32(const float* x, const uint8_t* mask, const float* dy, int64_t P, int C,
+                              int ldx, int ldm, int lddy, const float* mean, const float* invstd,
+                              const float* weight, const double* sums, double count, int act, float slope,
+                              float* dx, int lddx, float* dres, int lddres,
+                              float* dweight, float* dbias, void* stream);
+/* ssg_bn_bwd_apply_f32 in the block geometry of the column reducers, which also returns dxsum[c] = sum_p dx[p][c] with the bits
+ * of ssg_channel_sum_f32(dx): the bias gradient of the conv in front of the batch norm, without a pass over the fresh dx.
+ * The activation mask comes from `mask` (1-bit form), else from y, else (both NULL) is recomputed from x with (scale, shift).
+ * act: none, ReLU or LeakyReLU.  dx is required; ws: ssg_bn_workspace_bytes(P, C) bytes. */
+int ssg_bn_bwd_apply_sums_f32(const float* x, const float* y, const uint8_t* mask, const float* dy, int64_t P, int C,
+                              int ldx, int ldy, int ldm, int lddy, const float* mean, const float* invstd,
+                              const float* weight, const float* scale, const float* shift,
+                              const double* sums, double count, int act, float slope,
+                              float* dx, int lddx, float* dres, int lddres,
+                              float* dweight, float* dbias, float* dxsum, void* ws, void* stream);
 /* eval-mode / generic per-channel affine: y = x*scale + shift -> act (also used for bias+act) */
 /* Backward of a batch norm whose statistics are CONSTANTS (eval mode / frozen: torch.nn.functional.batch_norm(training=False),
  * archs.py:211,213 under model.eval()), in one pass -- no per-batch mean to subtract, so the stores ride the reduction sweep:

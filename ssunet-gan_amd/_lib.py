@@ -135,6 +135,11 @@ SIGNATURES = {
     'ssg_bn_apply_f32': [_P, _L, _I, _I, _P, _P, _P, _I, _I, _F, _P, _I, _P],
     'ssg_bn_bwd_reduce_f32': [_P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _I, _P, _P],
     'ssg_bn_bwd_apply_f32': [_P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _D, _I, _F, _P, _I, _P, _I, _P, _P, _P],
+    'ssg_bn_mask_ok': [_I, _I],
+    'ssg_bn_apply_mask_f32': [_P, _L, _I, _I, _P, _P, _P, _I, _I, _F, _P, _I, _P, _I, _P],
+    'ssg_bn_bwd_reduce_mask_f32': [_P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _I, _F, _P, _I, _P, _P],
+    'ssg_bn_bwd_apply_mask_f32': [_P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _D, _I, _F, _P, _I, _P, _I, _P, _P, _P],
+    'ssg_bn_bwd_apply_sums_f32': [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _D, _I, _F, _P, _I, _P, _I, _P, _P, _P, _P, _P],
     'ssg_bn_frozen_bwd_f32': [_P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _I, _P, _I, _P, _P, _P],
     'ssg_bn_fold_bwd_f32': [_P, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P, _P],
     'ssg_maxpool2x2_fwd_f32': [_P, _I, _I, _I, _I, _I, _P, _I, _P, _P],
@@ -244,7 +249,7 @@ _RESTYPES = {
     'ssg_bn_stats_from_partials_workspace_bytes': C.c_int64,
 }
 _NO_STATUS = set(_RESTYPES) | {'ssg_abi_version', 'ssg_conv2d_split_bn', 'ssg_conv2d_in_affine_ok', 'ssg_conv2d_wgrad_in_affine_ok', 'ssg_conv2d_bwd_stats_ok', 'ssg_conv2d_kernel_id', 'ssg_conv2d_bnpart_rows', 'ssg_conv2d_bf16x1_ok', 'ssg_conv2d_bf16x1_kernel_id', 'ssg_conv2d_bf16x2_ok', 'ssg_conv2d_bf16x2_kernel_id', 'ssg_conv2d_wgrad_bf16x2_ok', 'ssg_conv2d_wgrad_bf16x2_kernel_id', 'ssg_conv2d_bf16x1_s2_ok', 'ssg_conv2d_bf16x1_s2_kernel_id', 'ssg_conv2d_bf16x1_cls_ok', 'ssg_conv2d_bf16x1_cls_kernel_id', 'ssg_conv2d_wgrad_bf16x1_ok', 'ssg_conv2d_wgrad_bf16x1_kernel_id', 'ssg_conv2d_wgrad_bf16x1_s2_ok', 'ssg_conv2d_wgrad_bf16x1_s2_kernel_id', 'ssg_conv2d_wgrad_kernel_id', 'ssg_dwconv2d_kernel_id',
-                                'ssg_spade_conv_modulate_ok', 'ssg_se_gate_ok', 'ssg_spade_dgrad_modulate_ok'}
+                                'ssg_spade_conv_modulate_ok', 'ssg_se_gate_ok', 'ssg_spade_dgrad_modulate_ok', 'ssg_bn_mask_ok'}
 
 ABI_VERSION = 10         # ssg_abi_version() of the library this ctypes table (ConvDesc layout, SIGNATURES) was written against
 

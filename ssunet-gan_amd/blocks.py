@@ -65,15 +65,16 @@ class _BasicBlockFn(torch.autograd.Function):
             if x2 is not None:
                 raise ValueError('identity shortcut with a two-tensor input')
             sc = x1
-        out, st2, cnt2 = _bn_fwd_impl(c2, g2, b2, rm2, rv2, sc, eps2, mom2, ACT_RELU, 0.0, var_mode, group, part=part2)
-        ctx.save_for_backward(x1, x2, c1, y1, c2, out, w1, g1, w2, g2, wsc, st1, st2)      # y1 = None on the fused route
+        # the final ReLU's mask in C / 8 bytes per pixel where the kernels allow it (ops.BN_BWD_LEAN): `out` is then not kept
+        out, st2, cnt2, mask = _bn_fwd_impl(c2, g2, b2, rm2, rv2, sc, eps2, mom2, ACT_RELU, 0.0, var_mode, group, part=part2, want_mask=True)
+        ctx.save_for_backward(x1, x2, c1, y1, c2, out if mask is None else None, w1, g1, w2, g2, wsc, st1, st2, mask)   # y1 = None on the fused route
         ctx.cfg = (stride, group, cnt1, cnt2)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dout):
-        x1, x2, c1, y1, c2, out, w1, g1, w2, g2, wsc, st1, st2 = ctx.saved_tensors
+        x1, x2, c1, y1, c2, out, w1, g1, w2, g2, wsc, st1, st2, mask = ctx.saved_tensors
         stride, group, cnt1, cnt2 = ctx.cfg
         x1m = ctx.x1m                                    # the forward's train_precision mode, whatever is set now
         p3 = x1m or 'fp32'
@@ -82,7 +83,7 @@ class _BasicBlockFn(torch.autograd.Function):
         cb = x2.shape[1] if x2 is not None else 0
         need_x1, need_x2 = ctx.needs_input_grad[0], (x2 is not None and ctx.needs_input_grad[1])
         # bn2 backward; dres = dout masked by the final ReLU = gradient of the shortcut branch
-        dc2, g, dg2, db2 = _bn_bwd_impl(c2, out, dout, g2, st2, ACT_RELU, 0.0, group, cnt2, want_dres=True)
+        dc2, g, dg2, db2 = _bn_bwd_impl(c2, out, dout, g2, st2, ACT_RELU, 0.0, group, cnt2, want_dres=True, mask=mask)
         if y1 is None:                                   # fused route: conv2 read relu(bn1(c1)) through its input transform
             dw2 = _conv_wgrad_impl(c1, None, dc2, w2.shape, 1, 1, in_affine=(st1[2], st1[3], ACT_RELU, 0.0))
             if dw2 is None:                              # no weight-gradient kernel with the transform for this shape: write y1 now
@@ -283,6 +284,8 @@ def _spade_fused_fwd(x, a, wgb, bgb, pad, out):
 # less than the launch of the second weight-gradient kernel and its reduce stage that the lean sequence adds.
 SPADE_BWD_LEAN = {'0': 0, '2': 2}.get(os.environ.get('SSG_SPADE_BWD_LEAN', '1'), 1)
 SPADE_BWD_LEAN_MIN = 1 << 20
+# The batch-norm backward has the same kind of switch, SSG_BN_BWD_LEAN, and its threshold ops.BN_BWD_LEAN_MIN: they live in ops.py,
+# beside the nodes that read them (ops._BatchNormAct, ops._ConvBnAct, ops._Conv2d); _BasicBlockFn above asks through _bn_fwd_impl.
 
 
 def _dgrad_taps(kh, kw, pad):

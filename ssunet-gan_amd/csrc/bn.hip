@@ -37,7 +37,9 @@ __host__ RedGeom red_geom(long long P, int C, int Q = 1) {
 // MODE 3: MODE 1 that also stores what a batch norm with CONSTANT statistics (eval mode, or a bias + activation) needs of the
 //         sweep: dx = g * scale (scale = NULL: g), dres = g.  x / mean may be NULL there (no xhat sum; x only where the
 //         activation gradient is recomputed from it).  Same accumulation expressions as MODE 1: the sums carry the same bits.
-template <int MODE, typename T>
+// BITS: `y` points at the forward's 1-bit mask instead (uint8 [P][ldy bytes], bit c % 8 of byte c / 8 = y[p][c] > 0: fp32 tensors,
+//         ReLU family, MODE 1).  Same per-element products and sums as the test on y itself: the partial rows carry the same bits.
+template <int MODE, typename T, bool BITS = false>
 __global__ __launch_bounds__(RED_BLOCK) void col_reduce_kernel(
     const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy, long long P, int C,
     int ldx, int ldy, int lddy, const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -46,6 +48,7 @@ __global__ __launch_bounds__(RED_BLOCK) void col_reduce_kernel(
     T* __restrict__ dx, int lddx, T* __restrict__ dres, int lddres /* MODE 3 only */) {
   constexpr int Q = SsgQ<T>::value;              // channel quads per 16-byte access
   constexpr int V = 4 * Q;
+  static_assert(!BITS || (Q == 1 && MODE == 1), "the 1-bit mask form is the fp32 MODE 1 reduce");
   __shared__ double red[2][RED_BLOCK][V];
   const int tid = threadIdx.x;
   const int tq = tid % TQ, pr = tid / TQ;
@@ -104,7 +107,9 @@ __global__ __launch_bounds__(RED_BLOCK) void col_reduce_kernel(
         f32x4 gq[Q], yq[Q];
         ldq(dy + p * lddy + V * cg, gq);
         const bool use_y = act != SSG_ACT_NONE && act != SSG_ACT_SWISH && y;
-        if (use_y) ldq(y + p * ldy + V * cg, yq);
+        unsigned mb = 0;                           // BITS: this quad's four mask bits (two quads share a byte)
+        if (BITS) mb = (unsigned)((const uint8_t*)y)[p * ldy + (cg >> 1)] >> (4 * (cg & 1));
+        else if (use_y) ldq(y + p * ldy + V * cg, yq);
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
 #pragma unroll
@@ -112,7 +117,9 @@ __global__ __launch_bounds__(RED_BLOCK) void col_reduce_kernel(
             const int k = 4 * q + e;
             float g = gq[q][e];
             const float xv = xq[q][e];
-            if (act == SSG_ACT_SWISH) {
+            if (BITS) {
+              if (!((mb >> k) & 1u)) g *= (act == SSG_ACT_RELU ? 0.f : slope);
+            } else if (act == SSG_ACT_SWISH) {
               // smooth activation: its derivative is a function of the pre-activation z = x*scale + shift (recomputed)
               g *= ssg_swish_grad(xv * sc[k] + sh[k]);
             } else if (act != SSG_ACT_NONE) {
@@ -338,13 +345,64 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, 
   }
 }
 
-template <typename T>
+// Forward apply that also packs the sign of what it stores: mask[p][c / 8] bit c % 8 = y[p][c] > 0.  The loop of bn_apply_kernel,
+// one channel quad per thread (an 8-channel group per thread -- one byte per thread, no cross-lane work -- strides the lanes'
+// 16-byte accesses 32 bytes apart and ran at 4.3 TB/s where this form runs at the plain kernel's rate): a thread forms the four
+// bits of its quad, takes the other half of the byte from its neighbour lane with one DPP move, and the even lane stores it.
+// The two quads of a byte sit in lanes 2k, 2k + 1 of one wave in the same iteration: chunks start at multiples of 256, C / 4 and
+// with it the total are even, so an index has the parity of its lane and a pair is inside the range or outside it together.
+// y: the expression of bn_apply_kernel, operation for operation.
+__global__ __launch_bounds__(256) void bn_apply_mask_kernel(const float* __restrict__ x, long long P, int C, int ld,
+                                                            const float* __restrict__ scale, const float* __restrict__ shift,
+                                                            const float* __restrict__ res, int ldr, int act, float slope,
+                                                            float* __restrict__ y, int ldy, uint8_t* __restrict__ mask, int ldm) {
+  const int CG = C / 4;
+  const long long total = P * CG;
+  SSG_CHUNK_LOOP(i, total) {
+    const long long p = i / CG; const int cq = (int)(i - p * CG); const int c0 = 4 * cq;
+    const f32x4 xv = *(const f32x4*)(x + p * ld + c0);
+    f32x4 rv = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (res) rv = *(const f32x4*)(res + p * ldr + c0);
+    const f32x4 sc = *(const f32x4*)(scale + c0), sh = *(const f32x4*)(shift + c0);
+    f32x4 v = xv * sc + sh;
+    if (res) v += rv;
+    unsigned nib = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[e] = ssg_act(v[e], act, slope);
+      nib |= (v[e] > 0.f ? 1u : 0u) << e;
+    }
+    st4(y + p * ldy + c0, v);
+    const unsigned other = (unsigned)__builtin_amdgcn_mov_dpp((int)nib, 0xB1, 0xf, 0xf, false);     // quad_perm [1,0,3,2]: lane ^ 1
+    if (!(cq & 1)) mask[p * ldm + (cq >> 1)] = (uint8_t)(nib | (other << 4));
+  }
+}
+
+// One element of the batch-norm input gradient, dx = w*invstd * (g - mean(g) - xhat * mean(g*xhat)), shared by the two apply
+// kernels.  The multiply-add is an EXPLICIT fma for the reason given at bn_finalize_channel: hipcc contracts per inlining
+// context, and the two kernels must store the same bits.
+// fp64 arithmetic for fp32 tensors, as ATen's CPU batch-norm backward (accscalar = double for float tensors):
+// g - mean(g) - xhat*mean(g*xhat) cancels heavily, and an fp32-rounded per-channel constant
+// would add the SAME error to every pixel (a coherent bias that the next dgrad/bias-grad
+// sums amplify).  The kernels are HBM-bound; fp64 VALU work is free here.
+__device__ __forceinline__ float bn_dx_elem(float g, float xv, double k_mean, double k_is, double k_ws, double k_m1, double k_m2) {
+  const double xh = ((double)xv - k_mean) * k_is;
+  return (float)(k_ws * fma(-xh, k_m2, (double)g - k_m1));
+}
+__device__ __forceinline__ float bn_dx_elem(float g, float xv, float k_mean, float k_is, float k_ws, float k_m1, float k_m2) {
+  const float xh = (xv - k_mean) * k_is;
+  return k_ws * fmaf(-xh, k_m2, g - k_m1);
+}
+
+// BITS: `y` points at the forward's 1-bit mask (see col_reduce_kernel); fp32 tensors, ReLU family.
+template <typename T, bool BITS = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy, long long P, int C, int ldx,
     int ldy, int lddy, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ weight,
     const float* __restrict__ scale, const float* __restrict__ shift,
     const double* __restrict__ sums, double count_arg, int act, float slope, T* __restrict__ dx, int lddx,
     T* __restrict__ dres, int lddres, float* __restrict__ dweight, float* __restrict__ dbias) {
+  static_assert(!BITS || SsgQ<T>::value == 1, "the 1-bit mask form is fp32 only");
   const double count = count_arg > 0 ? count_arg : sums[2 * C];
   if (blockIdx.x == 0) {
     for (int c = threadIdx.x; c < C; c += 256) {
@@ -373,13 +431,18 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     ldq(dy + p * lddy + c0, gq);
     ldq(x + p * ldx + c0, xq);
     const bool use_y = act != SSG_ACT_NONE && act != SSG_ACT_SWISH && y;
-    if (use_y) ldq(y + p * ldy + c0, yq);
+    unsigned mb = 0;
+    if (BITS) mb = (unsigned)((const uint8_t*)y)[p * ldy + (c0 >> 3)] >> (c0 & 4);
+    else if (use_y) ldq(y + p * ldy + c0, yq);
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
       const int cb = c0 + 4 * q;
       f32x4 g = gq[q];
       const f32x4 xv = xq[q];
-      if (act == SSG_ACT_SWISH) {
+      if (BITS) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (!((mb >> e) & 1u)) g[e] *= (act == SSG_ACT_RELU ? 0.f : slope);
+      } else if (act == SSG_ACT_SWISH) {
         const f32x4 z = xv * *(const f32x4*)(scale + cb) + *(const f32x4*)(shift + cb);
 #pragma unroll
         for (int e = 0; e < 4; ++e) g[e] *= ssg_swish_grad(z[e]);
@@ -391,15 +454,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
       gq[q] = g;
       if (dx) {
         f32x4 o;
-        // fp64 arithmetic, as ATen's CPU batch-norm backward (accscalar = double for float tensors):
-        // g - mean(g) - xhat*mean(g*xhat) cancels heavily, and an fp32-rounded per-channel constant
-        // would add the SAME error to every pixel (a coherent bias that the next dgrad/bias-grad
-        // sums amplify).  The kernel is HBM-bound; fp64 VALU work is free here.
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int c = cb + e;
-          const acc_t xh = ((acc_t)xv[e] - k_mean[c]) * k_is[c];
-          o[e] = (float)(k_ws[c] * ((acc_t)g[e] - k_m1[c] - xh * k_m2[c]));
+          o[e] = bn_dx_elem(g[e], xv[e], k_mean[c], k_is[c], k_ws[c], k_m1[c], k_m2[c]);
         }
         oq[q] = o;
       }
@@ -409,9 +467,95 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
   }
 }
 
+// The apply pass in the reducer's block geometry (red_geom: a fixed channel quad per thread, strided pixels): writes dx (and
+// dres) and carries (double) of every stored dx value into the partial rows col_reduce_kernel<2> gives on that tensor -- same
+// per-thread order, same LDS fold, finished by col_reduce_final_kernel -- so sum(dx), the bias gradient of the conv in front of
+// the batch norm, costs no pass of its own and has the bits of ssg_channel_sum_f32(dx).  fp32, ReLU family or no activation.
+// BITS: `y` is the 1-bit mask.
+template <bool BITS>
+__global__ __launch_bounds__(RED_BLOCK) void bn_bwd_apply_sums_kernel(
+    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dy, long long P, int C, int ldx,
+    int ldy, int lddy, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ weight,
+    const float* __restrict__ scale, const float* __restrict__ shift,
+    const double* __restrict__ sums, double count_arg, int act, float slope, float* __restrict__ dx, int lddx,
+    float* __restrict__ dres, int lddres, float* __restrict__ dweight, float* __restrict__ dbias,
+    int TQ, int PR, long long rows_per_part, double* __restrict__ part /* [parts][2][C] */) {
+  __shared__ double red[RED_BLOCK][4];
+  __shared__ double kc[5][RED_BLOCK];            // mean, invstd, w*invstd, m1, m2 of this block's 4 * TQ <= 256 channels
+  const double count = count_arg > 0 ? count_arg : sums[2 * C];
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0 && blockIdx.y == 0) {
+    for (int c = tid; c < C; c += RED_BLOCK) {
+      if (dweight) dweight[c] = (float)sums[C + c];
+      if (dbias) dbias[c] = (float)sums[c];
+    }
+  }
+  const int tq = tid % TQ, pr = tid / TQ;
+  const int cg = blockIdx.y * TQ + tq;           // channel quad
+  const int CG = C / 4;
+  const bool cok = cg < CG;
+  if (tid < 4 * TQ) {
+    const int c = 4 * (int)blockIdx.y * TQ + tid;
+    if (c < C) {
+      const double is = (double)invstd[c];
+      kc[0][tid] = (double)mean[c]; kc[1][tid] = is; kc[2][tid] = (weight ? (double)weight[c] : 1.0) * is;
+      kc[3][tid] = sums[c] / count; kc[4][tid] = sums[C + c] / count;
+    }
+  }
+  __syncthreads();
+  const long long p0 = (long long)blockIdx.x * rows_per_part;
+  long long p1 = p0 + rows_per_part; if (p1 > P) p1 = P;
+  double s1[4] = {0, 0, 0, 0};
+  if (cok) {
+    double k_mean[4], k_is[4], k_ws[4], k_m1[4], k_m2[4];
+    f32x4 sc = f32x4{0.f, 0.f, 0.f, 0.f}, sh = sc;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      k_mean[e] = kc[0][4 * tq + e]; k_is[e] = kc[1][4 * tq + e]; k_ws[e] = kc[2][4 * tq + e];
+      k_m1[e] = kc[3][4 * tq + e]; k_m2[e] = kc[4][4 * tq + e];
+    }
+    const bool use_y = act != SSG_ACT_NONE && y;
+    if (!BITS && act != SSG_ACT_NONE && !y) { sc = *(const f32x4*)(scale + 4 * cg); sh = *(const f32x4*)(shift + 4 * cg); }
+    for (long long p = p0 + pr; p < p1; p += PR) {
+      f32x4 g = *(const f32x4*)(dy + p * lddy + 4 * cg);
+      const f32x4 xv = *(const f32x4*)(x + p * ldx + 4 * cg);
+      if (BITS) {
+        const unsigned mb = (unsigned)((const uint8_t*)y)[p * ldy + (cg >> 1)] >> (4 * (cg & 1));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (!((mb >> e) & 1u)) g[e] *= (act == SSG_ACT_RELU ? 0.f : slope);
+      } else if (act != SSG_ACT_NONE) {
+        // the forward's own expression where it had no residual (bn_bwd_apply_kernel): bitwise the same sign
+        const f32x4 yv = use_y ? *(const f32x4*)(y + p * ldy + 4 * cg) : xv * sc + sh;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (!(yv[e] > 0.f)) g[e] *= (act == SSG_ACT_RELU ? 0.f : slope);
+      }
+      if (dres) st4(dres + p * lddres + 4 * cg, g);
+      f32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        o[e] = bn_dx_elem(g[e], xv[e], k_mean[e], k_is[e], k_ws[e], k_m1[e], k_m2[e]);
+        s1[e] += (double)o[e];
+      }
+      st4(dx + p * lddx + 4 * cg, o);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) red[tid][e] = s1[e];
+  __syncthreads();
+  if (pr == 0 && cok) {
+    double a1[4] = {0, 0, 0, 0};
+    for (int r = 0; r < PR; ++r)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a1[e] += red[r * TQ + tq][e];
+    double* dst = part + (size_t)blockIdx.x * 2 * C;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { dst[4 * cg + e] = a1[e]; dst[C + 4 * cg + e] = 0.0; }
+  }
+}
+
 int elem_grid(long long total) { return ssg_elem_grid(total, 4); }     // 4 items per thread: bn_bwd_apply has a per-block prologue (5 fp64 constants per channel)
 
-template <int MODE, typename T>
+template <int MODE, typename T, bool BITS = false>
 int run_reduce(const T* x, const T* y, const T* dy, long long P, int C, int ldx, int ldy, int lddy,
                const float* scale, const float* shift,
                const float* mean, const float* invstd, int act, float slope, double* sums, float* fsum, void* ws,
@@ -420,7 +564,7 @@ int run_reduce(const T* x, const T* y, const T* dy, long long P, int C, int ldx,
   const RedGeom g = red_geom(P, C, Q);
   const int C4 = 4 * Q * ((C + 4 * Q - 1) / (4 * Q));
   double* part = (double*)ws;
-  hipLaunchKernelGGL((col_reduce_kernel<MODE, T>), dim3((unsigned)g.parts, (unsigned)g.groups), dim3(RED_BLOCK), 0, st, x, y, dy,
+  hipLaunchKernelGGL((col_reduce_kernel<MODE, T, BITS>), dim3((unsigned)g.parts, (unsigned)g.groups), dim3(RED_BLOCK), 0, st, x, y, dy,
                      P, C, ldx, ldy, lddy, mean, invstd, scale, shift, act, slope, g.TQ, g.PR, g.rows_per_part, part, (T*)nullptr, 0, (T*)nullptr, 0);
   SSG_LAUNCH_CHECK();
   hipLaunchKernelGGL(col_reduce_final_kernel, dim3((unsigned)((C + 31) / 32)), dim3(32 * FIN_LANES), 0, st, part, g.parts, C, C4, sums, fsum, count_out, fin, fin_count);
@@ -647,6 +791,100 @@ extern "C" int ssg_bn_bwd_apply_bf16(const void* x, const void* y, const void* d
                                      float* dweight, float* dbias, void* stream) {
   return bn_bwd_apply_impl<ssg_bf16>((const ssg_bf16*)x, (const ssg_bf16*)y, (const ssg_bf16*)dy, P, C, ldx, ldy, lddy, mean, invstd, weight, scale,
                                      shift, sums, count, act, slope, (ssg_bf16*)dx, lddx, (ssg_bf16*)dres, lddres, dweight, dbias, stream);
+}
+
+// ------------------------------------------------------------------ 1-bit activation masks, column sums of dx from the apply pass
+// Where the forward had a residual the backward needs sign(y) and nothing else of y: the forward packs it (C / 8 bytes per pixel
+// instead of 4 * C), and the two backward passes read the bytes where they read y.
+extern "C" int ssg_bn_mask_ok(int C, int act) { return C > 0 && C % 8 == 0 && (act == SSG_ACT_RELU || act == SSG_ACT_LRELU); }
+
+namespace {
+// a mask operand: the predicate, a row stride that holds C / 8 bytes (rows need no alignment: byte accesses)
+bool mask_args_ok(const void* mask, int C, int ldm, int act) { return mask && ssg_bn_mask_ok(C, act) && ldm >= C / 8; }
+}  // namespace
+
+extern "C" int ssg_bn_apply_mask_f32(const float* x, int64_t P, int C, int ld, const float* scale, const float* shift, const float* res,
+                                     int ldr, int act, float slope, float* y, int ldy, uint8_t* mask, int ldm, void* stream) {
+  SSG_REQUIRE(x && y && scale && shift && P > 0 && C > 0, SSG_EINVAL, "bn_apply_mask: bad args");
+  SSG_REQUIRE(mask_args_ok(mask, C, ldm, act), SSG_EINVAL, "bn_apply_mask: needs a mask, C %% 8 == 0, ldm >= C / 8 and a ReLU-family activation");
+  SSG_REQUIRE(ld % 4 == 0 && ld >= C && ldy % 4 == 0 && ldy >= C && (!res || (ldr % 4 == 0 && ldr >= C)) && ssg_aligned16(x) && ssg_aligned16(y) &&
+                  (!res || ssg_aligned16(res)), SSG_EALIGN, "bn_apply_mask: ld must be multiples of 4 and >= C, rows 16-byte aligned");
+  hipLaunchKernelGGL(bn_apply_mask_kernel, dim3((unsigned)elem_grid(P * (C / 4))), dim3(256), 0, (hipStream_t)stream, x, (long long)P, C, ld,
+                     scale, shift, res, ldr, act, slope, y, ldy, mask, ldm);
+  SSG_LAUNCH_CHECK();
+  return SSG_OK;
+}
+
+extern "C" int ssg_bn_bwd_reduce_mask_f32(const float* x, const uint8_t* mask, const float* dy, int64_t P, int C, int ldx, int ldm, int lddy,
+                                          const float* mean, const float* invstd, int act, float slope, double* sums, int with_count,
+                                          void* ws, void* stream) {
+  SSG_REQUIRE(x && dy && mean && invstd && sums && ws && P > 0 && C > 0, SSG_EINVAL, "bn_bwd_reduce_mask: bad args");
+  SSG_REQUIRE(mask_args_ok(mask, C, ldm, act), SSG_EINVAL, "bn_bwd_reduce_mask: needs a mask, C %% 8 == 0, ldm >= C / 8 and a ReLU-family activation");
+  SSG_REQUIRE(ldx % 4 == 0 && ldx >= C && lddy % 4 == 0 && lddy >= C && ssg_aligned16(x) && ssg_aligned16(dy), SSG_EALIGN,
+              "bn_bwd_reduce_mask: ld must be multiples of 4 and >= C, rows 16-byte aligned");
+  return run_reduce<1, float, true>(x, (const float*)mask, dy, P, C, ldx, ldm, lddy, nullptr, nullptr, mean, invstd, act, slope, sums, nullptr, ws,
+                                    (hipStream_t)stream, with_count ? (double)P : 0.0);
+}
+
+namespace {
+int bwd_apply_common_ok(const char* who, const float* x, const float* dy, int64_t P, int C, int ldx, int lddy, const float* mean,
+                        const float* invstd, const double* sums, const float* dx, int lddx, const float* dres, int lddres) {
+  SSG_REQUIRE(x && dy && mean && invstd && sums && P > 0 && C > 0, SSG_EINVAL, "%s: bad args", who);
+  SSG_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldx >= C && lddy % 4 == 0 && lddy >= C && (!dx || (lddx % 4 == 0 && lddx >= C)) &&
+                  (!dres || (lddres % 4 == 0 && lddres >= C)) && ssg_aligned16(x) && ssg_aligned16(dy) && ssg_aligned16(dx) && ssg_aligned16(dres),
+              SSG_EALIGN, "%s: C / ld must be multiples of 4, ld >= C, rows 16-byte aligned", who);
+  SSG_REQUIRE(C <= 4096, SSG_EINVAL, "%s: C > 4096", who);
+  return SSG_OK;
+}
+}  // namespace
+
+extern "C" int ssg_bn_bwd_apply_mask_f32(const float* x, const uint8_t* mask, const float* dy, int64_t P, int C, int ldx, int ldm, int lddy,
+                                         const float* mean, const float* invstd, const float* weight, const double* sums, double count,
+                                         int act, float slope, float* dx, int lddx, float* dres, int lddres, float* dweight, float* dbias,
+                                         void* stream) {
+  const int rc = bwd_apply_common_ok("bn_bwd_apply_mask", x, dy, P, C, ldx, lddy, mean, invstd, sums, dx, lddx, dres, lddres);
+  if (rc != SSG_OK) return rc;
+  SSG_REQUIRE(mask_args_ok(mask, C, ldm, act), SSG_EINVAL, "bn_bwd_apply_mask: needs a mask, C %% 8 == 0, ldm >= C / 8 and a ReLU-family activation");
+  if ((size_t)5 * C * sizeof(double) > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)bn_bwd_apply_kernel<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * C * (int)sizeof(double));
+    if (e != hipSuccess) { ssg_set_error("bn_bwd_apply_mask: LDS attribute: %s", hipGetErrorString(e)); return (int)e; }
+  }
+  hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), dim3((unsigned)elem_grid(P * (C / 4))), dim3(256), (size_t)5 * C * sizeof(double), (hipStream_t)stream,
+                     x, (const float*)mask, dy, (long long)P, C, ldx, ldm, lddy, mean, invstd, weight, (const float*)nullptr, (const float*)nullptr, sums,
+                     count, act, slope, dx, lddx, dres, lddres, dweight, dbias);
+  SSG_LAUNCH_CHECK();
+  return SSG_OK;
+}
+
+extern "C" int ssg_bn_bwd_apply_sums_f32(const float* x, const float* y, const uint8_t* mask, const float* dy, int64_t P, int C, int ldx, int ldy,
+                                         int ldm, int lddy, const float* mean, const float* invstd, const float* weight, const float* scale,
+                                         const float* shift, const double* sums, double count, int act, float slope, float* dx, int lddx,
+                                         float* dres, int lddres, float* dweight, float* dbias, float* dxsum, void* ws, void* stream) {
+  const int rc = bwd_apply_common_ok("bn_bwd_apply_sums", x, dy, P, C, ldx, lddy, mean, invstd, sums, dx, lddx, dres, lddres);
+  if (rc != SSG_OK) return rc;
+  SSG_REQUIRE(dx && dxsum && ws, SSG_EINVAL, "bn_bwd_apply_sums: dx, dxsum and ws are required");
+  SSG_REQUIRE(act == SSG_ACT_NONE || act == SSG_ACT_RELU || act == SSG_ACT_LRELU, SSG_EINVAL, "bn_bwd_apply_sums: ReLU family or no activation only");
+  SSG_REQUIRE(!(y && mask), SSG_EINVAL, "bn_bwd_apply_sums: y or mask, not both");
+  SSG_REQUIRE(!mask || mask_args_ok(mask, C, ldm, act), SSG_EINVAL,
+              "bn_bwd_apply_sums: a mask needs C %% 8 == 0, ldm >= C / 8 and a ReLU-family activation");
+  SSG_REQUIRE(act == SSG_ACT_NONE || mask || y || (scale && shift), SSG_EINVAL, "bn_bwd_apply_sums: activation gradient needs y, mask or (scale, shift)");
+  SSG_REQUIRE(!y || act == SSG_ACT_NONE || (ldy % 4 == 0 && ldy >= C && ssg_aligned16(y)), SSG_EALIGN, "bn_bwd_apply_sums: y alignment");
+  const RedGeom g = red_geom(P, C, 1);
+  double* part = (double*)ws;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)g.parts, (unsigned)g.groups);
+  if (mask)
+    hipLaunchKernelGGL(bn_bwd_apply_sums_kernel<true>, grid, dim3(RED_BLOCK), 0, st, x, (const float*)mask, dy, (long long)P, C, ldx, ldm, lddy, mean,
+                       invstd, weight, scale, shift, sums, count, act, slope, dx, lddx, dres, lddres, dweight, dbias, g.TQ, g.PR, g.rows_per_part, part);
+  else
+    hipLaunchKernelGGL(bn_bwd_apply_sums_kernel<false>, grid, dim3(RED_BLOCK), 0, st, x, y, dy, (long long)P, C, ldx, ldy, lddy, mean,
+                       invstd, weight, scale, shift, sums, count, act, slope, dx, lddx, dres, lddres, dweight, dbias, g.TQ, g.PR, g.rows_per_part, part);
+  SSG_LAUNCH_CHECK();
+  // the second stage of ssg_channel_sum_f32: same rows, same order, same bits
+  hipLaunchKernelGGL(col_reduce_final_kernel, dim3((unsigned)((C + 31) / 32)), dim3(32 * FIN_LANES), 0, st, part, g.parts, C, C, (double*)nullptr, dxsum, 0.0,
+                     BnFin{}, 0.0);
+  SSG_LAUNCH_CHECK();
+  return SSG_OK;
 }
 
 extern "C" int ssg_spade_modulate_bwd_sums_f32(const float* x, int ldx, const float* gb, int ldgb, const float* dy, int lddy, int64_t P,

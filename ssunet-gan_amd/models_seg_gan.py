@@ -68,12 +68,17 @@ class ConvolutionalBlock(nn.Module):
         if not self._bn:
             return run(act, slope)
         bn = self.conv_block[1]
+        group = getattr(bn, '_ssg_sync_group', None)
+        if sn is None and conv.bias is not None and ops.conv_bn_act_ok(input, conv.weight, bn):
+            # conv -> BN -> act as one autograd node: the conv's bias gradient rides the batch norm's backward apply pass
+            return ops.conv_bn_act(input, conv.weight, conv.bias, conv.stride[0], conv.padding[0], bn, act=act, slope=slope, group=group,
+                                   precision=precision, wgrad_s2=wgrad_s2)
         part = None
         if sn is None and bn.training:
             y, part = run(ACT_NONE, 0.0, bn_stats=True)       # (sum, sum of squares) of y from the conv epilogue
         else:
             y = run(ACT_NONE, 0.0)
-        return ops.batch_norm_act(y, bn, act=act, slope=slope, group=getattr(bn, '_ssg_sync_group', None), stats_part=part)
+        return ops.batch_norm_act(y, bn, act=act, slope=slope, group=group, stats_part=part)
 
 
 class Generator(nn.Module):

@@ -694,18 +694,26 @@ class _Conv2d(torch.autograd.Function):
         x1, x2, weight, y = ctx.saved_tensors
         stride, pad, act, slope, precision, wgrad_s2 = ctx.cfg
         dy = to_nhwc(dy)
-        if act != ACT_NONE:
-            dy = _act_bwd(y, dy, act, slope)
         n, c1, h, w = x1.shape
         dx1 = dx2 = dw = db = None
+        want_db = ctx.has_bias and ctx.needs_input_grad[3]
+        cout = weight.shape[0]
+        if (act in (ACT_RELU, ACT_LRELU) and want_db and cout % 4 == 0 and dy.shape[1] == cout and dy.dtype == torch.float32
+                and _bn_lean()):
+            # activation backward and bias gradient in one sweep over dy (the discriminator's stem): the masked gradient is written
+            # while its column sums are carried, instead of _act_bwd and a _channel_sum pass over what it wrote -- same bits
+            dy, _, sums = _frozen_bwd(None, y, dy, None, None, None, None, act, slope)
+            db = sums[:cout].float()
+        elif act != ACT_NONE:
+            dy = _act_bwd(y, dy, act, slope)
         if ctx.needs_input_grad[0]:
             dx1 = _conv_dgrad_impl(dy, weight, stride, pad, h, w, 0, c1, precision=precision, x1_s2=True)
         if x2 is not None and ctx.needs_input_grad[1]:
             dx2 = _conv_dgrad_impl(dy, weight, stride, pad, h, w, c1, c1 + x2.shape[1], precision=precision, x1_s2=True)
         if ctx.needs_input_grad[2]:
             dw = _conv_wgrad_impl(x1, x2, dy, weight.shape, stride, pad, precision=precision, wgrad_s2=wgrad_s2)
-        if ctx.has_bias and ctx.needs_input_grad[3]:
-            db = _channel_sum(dy, weight.shape[0])
+        if want_db and db is None:
+            db = _channel_sum(dy, cout)
         dres = dy if (ctx.has_res and ctx.needs_input_grad[8]) else None      # residual joins before the activation
         return dx1, dx2, dw, db, None, None, None, None, dres, None, None, None
 
@@ -1224,6 +1232,30 @@ _STATS_EPOCH = [0]
 
 BN_FUSED_FINALIZE = _os.environ.get('SSG_BN_FUSED_FINALIZE', '1') != '0'
 
+# SSG_BN_BWD_LEAN (like blocks.SPADE_BWD_LEAN): 0 = the sequence before DESIGN.md 3.25 -- a batch norm with a residual keeps its fp32
+# output for the backward's activation mask, and a conv bias gradient in front of a batch norm / behind an activation is a
+# ssg_channel_sum_f32 pass over the freshly written gradient; 1 = the lean one: the forward packs the mask into C / 8 bytes per pixel
+# (ssg_bn_apply_mask_f32) where ssg_bn_mask_ok allows it, ConvolutionalBlock's conv -> BN -> act is one node whose apply pass carries
+# sum(dx) (ssg_bn_bwd_apply_sums_f32), and a conv's activation backward and bias gradient are one ssg_bn_frozen_bwd_f32 sweep;
+# 2 = the same without the size threshold (tests).  Every lean form computes the bits of the sequence it replaces.
+# BN_BWD_LEAN_MIN (elements of the tensor) holds for the mask forms alone: they keep the launch count, so below a size the C / 8
+# extra bytes per pixel of the forward are all that changes.  Trace of the 16 x 512^2 step (profiles/r16_a_*): the residual layers
+# of 3.1 M and 8.4 M elements come out within +-3 us of the old sequence over their three launches, the 25 M one gains 34 us --
+# the threshold sits between them.  The other two forms drop a launch and a pass at every size and have no threshold.
+BN_BWD_LEAN = {'0': 0, '2': 2}.get(_os.environ.get('SSG_BN_BWD_LEAN', '1'), 1)
+BN_BWD_LEAN_MIN = 1 << 24
+
+
+def _bn_lean(numel=None):
+    """The lean switch; with `numel`, for a form that BN_BWD_LEAN_MIN governs."""
+    return BN_BWD_LEAN == 2 or (BN_BWD_LEAN == 1 and (numel is None or numel >= BN_BWD_LEAN_MIN))
+
+
+def _bn_mask_route(x, res, act):
+    """True where the forward of a batch norm saves the 1-bit mask instead of its output: a residual (without one the mask is
+    recomputed from x), fp32, and what ssg_bn_mask_ok asks of (C, act)."""
+    return bool(res is not None and x.dtype == torch.float32 and _bn_lean(x.numel()) and call('ssg_bn_mask_ok', x.shape[1], act))
+
 
 def bn_fin(weight, bias, eps, momentum, var_mode, running_mean, running_var, stats):
     """ctypes `ssg_bn_fin` over the given tensors (stats = [mean, invstd, scale, shift] rows)."""
@@ -1237,15 +1269,19 @@ def bn_fin(weight, bias, eps, momentum, var_mode, running_mean, running_var, sta
     return f
 
 
-def _bn_fwd_impl(x, weight, bias, running_mean, running_var, res, eps, momentum, act, slope, var_mode, group, part=None, apply=True):
+def _bn_fwd_impl(x, weight, bias, running_mean, running_var, res, eps, momentum, act, slope, var_mode, group, part=None, apply=True,
+                 want_mask=False):
     """Timed wrapper (bench.py `hbm_stages`): algorithmic bytes per SURVEY.md 8(d) -- 2 reads + 1 write of the tensor, one read
-    less when the statistics rode the producing conv's epilogue, one more for a residual."""
+    less when the statistics rode the producing conv's epilogue, one more for a residual (and the mask bytes where they are
+    written).  `want_mask`: returns (y, stats, count, mask) -- see _bn_fwd_body."""
     n, c, h, w = x.shape
     reads = (1 if (part is not None and part.numel() > 0) else 2) + (1 if res is not None else 0)
     if not apply:                 # statistics only (the consumer conv applies scale / shift / act on its input): no pass over x at all
         reads -= 1
-    with _hbm('bn_fwd', 4.0 * n * h * w * c * (reads + (1 if apply else 0))):
-        return _bn_fwd_body(x, weight, bias, running_mean, running_var, res, eps, momentum, act, slope, var_mode, group, part, apply)
+    masked = want_mask and apply and _bn_mask_route(x, res, act)
+    with _hbm('bn_fwd', 4.0 * n * h * w * c * (reads + (1 if apply else 0)) + (n * h * w * c / 8.0 if masked else 0.0)):
+        r = _bn_fwd_body(x, weight, bias, running_mean, running_var, res, eps, momentum, act, slope, var_mode, group, part, apply, masked)
+    return (r if masked else r + (None,)) if want_mask else r
 
 
 def _bn_apply(x, stats, res, act, slope):
@@ -1257,10 +1293,23 @@ def _bn_apply(x, stats, res, act, slope):
     return y
 
 
-def _bn_fwd_body(x, weight, bias, running_mean, running_var, res, eps, momentum, act, slope, var_mode, group, part=None, apply=True):
+def _bn_apply_mask(x, stats, res, act, slope):
+    """_bn_apply that also packs the sign of what it stores (ssg_bn_apply_mask_f32): returns (y, mask) -- the same y, and uint8
+    [pixels, C / 8] with bit c % 8 of byte c / 8 = y > 0."""
+    n, c, h, w = x.shape
+    y = new_nhwc(n, c, h, w, x.device)
+    mask = torch.empty((n * h * w, c // 8), dtype=torch.uint8, device=x.device)
+    call('ssg_bn_apply_mask_f32', ptr(x), n * h * w, c, _ld(x), ptr(stats[2]), ptr(stats[3]), ptr(res), _ld(res) if res is not None else 0,
+         act, slope, ptr(y), _ld(y), ptr(mask), c // 8, stream_ptr())
+    return y, mask
+
+
+def _bn_fwd_body(x, weight, bias, running_mean, running_var, res, eps, momentum, act, slope, var_mode, group, part=None, apply=True,
+                 masked=False):
     """stats -> (all-reduce) -> finalize -> apply.  Returns (y, stats[4,C], count): `count` is None for a local batch norm
     and, when synchronised, the fp64[1] device tensor holding the all-reduced pixel count (ranks may hold unequal batches:
-    the count travels with the sums instead of being assumed to be p * world)."""
+    the count travels with the sums instead of being assumed to be p * world).  `masked`: the apply also packs the 1-bit
+    activation mask (_bn_apply_mask), returned as a fourth."""
     n, c, h, w = x.shape
     if c % 4:
         raise ValueError('batch_norm: C %% 4 != 0 unsupported (C=%d)' % c)
@@ -1298,32 +1347,45 @@ def _bn_fwd_body(x, weight, bias, running_mean, running_var, res, eps, momentum,
              ptr(running_mean), ptr(running_var), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), stream_ptr())
     if running_mean is not None or running_var is not None:
         _STATS_EPOCH[0] += 1
+    cnt = sums[2 * c:] if synced else None
+    if apply and masked:
+        y, mask = _bn_apply_mask(x, stats, res, act, slope)
+        return y, stats, cnt, mask
     y = _bn_apply(x, stats, res, act, slope) if apply else None
-    return y, stats, (sums[2 * c:] if synced else None)
+    return y, stats, cnt
 
 
-def _bn_bwd_impl(x, y, dy, weight, stats, act, slope, group, count, want_dres, want_dx=True, had_res=True):
+def _bn_bwd_impl(x, y, dy, weight, stats, act, slope, group, count, want_dres, want_dx=True, had_res=True, mask=None, want_dxsum=False):
     """Timed wrapper (bench.py `hbm_stages`): algorithmic bytes per SURVEY.md 8(d) -- 3 reads + 1 write (x, dy, the mask source;
-    dx), plus the dres write where the forward had a residual."""
+    dx), plus the dres write where the forward had a residual.  With the 1-bit `mask` the mask source is C / 8 bytes per pixel
+    instead of a tensor."""
     n, c, h, w = x.shape
-    with _hbm('bn_bwd', 4.0 * n * h * w * c * (3 + (1 if want_dx else 0) + (1 if want_dres else 0))):
-        return _bn_bwd_body(x, y, dy, weight, stats, act, slope, group, count, want_dres, want_dx, had_res)
+    src = n * h * w * c / 8.0 if mask is not None else 4.0 * n * h * w * c
+    with _hbm('bn_bwd', 4.0 * n * h * w * c * (2 + (1 if want_dx else 0) + (1 if want_dres else 0)) + src):
+        return _bn_bwd_body(x, y, dy, weight, stats, act, slope, group, count, want_dres, want_dx, had_res, mask, want_dxsum)
 
 
-def _bn_bwd_body(x, y, dy, weight, stats, act, slope, group, count, want_dres, want_dx=True, had_res=True):
-    """Returns (dx, dres, dweight, dbias).  The activation mask is read from y, or -- when the forward had no
-    residual (`had_res=False`) -- recomputed from x with the forward's (scale, shift): y is then not read.
-    `count`: what _bn_fwd_impl returned (None = local batch norm)."""
+def _bn_bwd_body(x, y, dy, weight, stats, act, slope, group, count, want_dres, want_dx=True, had_res=True, mask=None, want_dxsum=False):
+    """Returns (dx, dres, dweight, dbias), and sum(dx) per channel as a fifth where `want_dxsum` (the apply pass carries it:
+    ssg_bn_bwd_apply_sums_f32, the bits of _channel_sum(dx)).  The activation mask is read from the 1-bit `mask` the forward
+    packed, else from y, or -- when the forward had no residual (`had_res=False`) -- recomputed from x with the forward's
+    (scale, shift): y is then not read.  `count`: what _bn_fwd_impl returned (None = local batch norm)."""
     n, c, h, w = x.shape
     p = n * h * w
     dev = x.device
     if act == ACT_NONE or not had_res:
+        y = mask = None
+    if mask is not None:
         y = None
     synced = count is not None
     ws = _ws(call('ssg_bn_workspace_bytes', p, c), dev)
     sums = torch.empty(2 * c + 1, dtype=torch.float64, device=dev)
-    call('ssg_bn_bwd_reduce_f32', ptr(x), ptr(y), ptr(dy), p, c, _ld(x), _ld(y) if y is not None else 0, _ld(dy),
-         ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), act, slope, ptr(sums), int(synced), ptr(ws), stream_ptr())
+    if mask is not None:
+        call('ssg_bn_bwd_reduce_mask_f32', ptr(x), ptr(mask), ptr(dy), p, c, _ld(x), mask.shape[1], _ld(dy),
+             ptr(stats[0]), ptr(stats[1]), act, slope, ptr(sums), int(synced), ptr(ws), stream_ptr())
+    else:
+        call('ssg_bn_bwd_reduce_f32', ptr(x), ptr(y), ptr(dy), p, c, _ld(x), _ld(y) if y is not None else 0, _ld(dy),
+             ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), act, slope, ptr(sums), int(synced), ptr(ws), stream_ptr())
     # local (un-reduced) sums are this rank's weight/bias gradients; data-parallel all-reduces them later
     local = sums.clone() if synced else sums
     if synced:
@@ -1331,13 +1393,26 @@ def _bn_bwd_body(x, y, dy, weight, stats, act, slope, group, count, want_dres, w
     dwb = torch.empty((2, c), dtype=torch.float32, device=dev)
     dx = new_nhwc(n, c, h, w, dev) if want_dx else None
     dres = new_nhwc(n, c, h, w, dev) if want_dres else None
-    call('ssg_bn_bwd_apply_f32', ptr(x), ptr(y), ptr(dy), p, c, _ld(x), _ld(y) if y is not None else 0, _ld(dy),
-         ptr(stats[0]), ptr(stats[1]), ptr(weight), ptr(stats[2]), ptr(stats[3]), ptr(sums), 0.0 if synced else float(p), act, slope,
-         ptr(dx), _ld(dx) if dx is not None else 0, ptr(dres), _ld(dres) if dres is not None else 0,
-         ptr(dwb[0]), ptr(dwb[1]), stream_ptr())
+    dxsum = None
+    if want_dxsum:
+        dxsum = torch.empty(c, dtype=torch.float32, device=dev)
+        call('ssg_bn_bwd_apply_sums_f32', ptr(x), ptr(y), ptr(mask), ptr(dy), p, c, _ld(x), _ld(y) if y is not None else 0,
+             mask.shape[1] if mask is not None else 0, _ld(dy), ptr(stats[0]), ptr(stats[1]), ptr(weight), ptr(stats[2]), ptr(stats[3]),
+             ptr(sums), 0.0 if synced else float(p), act, slope, ptr(dx), _ld(dx), ptr(dres), _ld(dres) if dres is not None else 0,
+             ptr(dwb[0]), ptr(dwb[1]), ptr(dxsum), ptr(ws), stream_ptr())
+    elif mask is not None:
+        call('ssg_bn_bwd_apply_mask_f32', ptr(x), ptr(mask), ptr(dy), p, c, _ld(x), mask.shape[1], _ld(dy),
+             ptr(stats[0]), ptr(stats[1]), ptr(weight), ptr(sums), 0.0 if synced else float(p), act, slope,
+             ptr(dx), _ld(dx) if dx is not None else 0, ptr(dres), _ld(dres) if dres is not None else 0,
+             ptr(dwb[0]), ptr(dwb[1]), stream_ptr())
+    else:
+        call('ssg_bn_bwd_apply_f32', ptr(x), ptr(y), ptr(dy), p, c, _ld(x), _ld(y) if y is not None else 0, _ld(dy),
+             ptr(stats[0]), ptr(stats[1]), ptr(weight), ptr(stats[2]), ptr(stats[3]), ptr(sums), 0.0 if synced else float(p), act, slope,
+             ptr(dx), _ld(dx) if dx is not None else 0, ptr(dres), _ld(dres) if dres is not None else 0,
+             ptr(dwb[0]), ptr(dwb[1]), stream_ptr())
     if synced:
         dwb = torch.stack([local[c:2 * c], local[:c]]).float()
-    return dx, dres, dwb[0], dwb[1]
+    return (dx, dres, dwb[0], dwb[1], dxsum) if want_dxsum else (dx, dres, dwb[0], dwb[1])
 
 
 # SSG_BN_BWD_EPILOGUE=1: bn1's backward sums of a residual block from the epilogue of conv2's input gradient (ssg_conv_desc.bwd_x) instead of
@@ -1397,28 +1472,31 @@ class _BatchNormAct(torch.autograd.Function):
             rm = torch.nn.functional.pad(running_mean, (0, c4 - c)) if running_mean is not None else None
             rv = torch.nn.functional.pad(running_var, (0, c4 - c), value=1.0) if running_var is not None else None
             y, stats, cnt = _bn_fwd_impl(x, wp, bp, rm, rv, res, eps, momentum, act, slope, var_mode, group)
+            mask = None
             if running_mean is not None:
                 running_mean.copy_(rm[:c])
             if running_var is not None:
                 running_var.copy_(rv[:c])
             weight = wp
         else:
-            y, stats, cnt = _bn_fwd_impl(x, weight, bias, running_mean, running_var, res, eps, momentum, act, slope, var_mode, group, part=part)
-        ctx.save_for_backward(x, y if (act != ACT_NONE and res is not None) else None, weight, stats)   # no residual: mask is recomputed
+            y, stats, cnt, mask = _bn_fwd_impl(x, weight, bias, running_mean, running_var, res, eps, momentum, act, slope, var_mode, group,
+                                               part=part, want_mask=True)
+        # no residual: mask is recomputed; with one, the packed mask where the forward wrote it, else y
+        ctx.save_for_backward(x, y if (act != ACT_NONE and res is not None and mask is None) else None, weight, stats, mask)
         ctx.cfg = (act, slope, group, cnt, res is not None, c)
         return _relabel(y, c) if c4 != c else y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
-        x, y, weight, stats = ctx.saved_tensors
+        x, y, weight, stats, mask = ctx.saved_tensors
         act, slope, group, cnt, has_res, c = ctx.cfg
         dy = to_nhwc(dy)
         c4 = x.shape[1]
         if c4 != c:
             dy = _relabel(dy, c4)
         dx, dres, dw, db = _bn_bwd_impl(x, y, dy, weight, stats, act, slope, group, cnt, has_res and ctx.needs_input_grad[5],
-                                        had_res=has_res)
+                                        had_res=has_res, mask=mask)
         if c4 != c:
             dx = _relabel(dx, c)
             dres = _relabel(dres, c) if dres is not None else None
@@ -1533,6 +1611,63 @@ def batch_norm_act(x, bn, res=None, act=ACT_NONE, slope=0.0, group=None, var_mod
         # (the kernel refuses the combination in any forward; said here by name where a graph would be recorded)
         raise NotImplementedError('batch_norm_act: swish with a residual has no backward (its derivative needs the pre-activation sum)')
     return _AffineAct.apply(x, bn_w, bn_b, mean, invstd, scale.contiguous(), shift.contiguous(), res, int(act), float(slope), record)
+
+
+class _ConvBnAct(torch.autograd.Function):
+    """conv (+bias) -> training-mode batch norm -> activation as ONE node (models_seg_gan.ConvolutionalBlock).  The forward is
+    the launches of conv2d(bn_stats=True) + batch_norm_act; in the backward the conv's bias gradient sum(dx of the batch norm)
+    comes out of the apply pass that writes dx (ssg_bn_bwd_apply_sums_f32) -- inside one node, so it travels in a local
+    variable -- instead of a _channel_sum pass over the fresh tensor.  Same kernels otherwise, same bits."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, bn_w, bn_b, running_mean, running_var, stride, pad, eps, momentum, act, slope, var_mode, group,
+                precision, wgrad_s2):
+        x = to_nhwc(x)
+        c, part = _conv_fwd_impl(x, None, weight, bias, stride, pad, ACT_NONE, 0.0, want_bn=True, precision=precision, x1_s2=True)
+        y, stats, cnt = _bn_fwd_impl(c, bn_w, bn_b, running_mean, running_var, None, eps, momentum, act, slope, var_mode, group, part=part)
+        ctx.save_for_backward(x, weight, c, bn_w, stats)
+        ctx.cfg = (stride, pad, act, slope, group, cnt, precision, wgrad_s2, bias is not None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight, c, bn_w, stats = ctx.saved_tensors
+        stride, pad, act, slope, group, cnt, precision, wgrad_s2, has_bias = ctx.cfg
+        dy = to_nhwc(dy)
+        need = ctx.needs_input_grad
+        want_db = bool(has_bias and need[2])
+        r = _bn_bwd_impl(c, None, dy, bn_w, stats, act, slope, group, cnt, want_dres=False, had_res=False, want_dxsum=want_db)
+        dc, dg, dbeta, db = r[0], r[2], r[3], (r[4] if want_db else None)
+        n, c1, h, w = x.shape
+        dx = _conv_dgrad_impl(dc, weight, stride, pad, h, w, 0, c1, precision=precision, x1_s2=True) if need[0] else None
+        dw = _conv_wgrad_impl(x, None, dc, weight.shape, stride, pad, precision=precision, wgrad_s2=wgrad_s2) if need[1] else None
+        return (dx, dw, db, dg, dbeta) + (None,) * 12
+
+
+def conv_bn_act_ok(x, weight, bn):
+    """Whether conv_bn_act takes this layer: the lean switch, a batch norm in training mode, fp32, and an output channel count
+    the batch-norm kernels run unpadded."""
+    return bool(_bn_lean() and bn.training and bn.momentum is not None and
+                x.dtype == torch.float32 and weight.shape[0] % 4 == 0)
+
+
+def conv_bn_act(x, weight, bias, stride, padding, bn, act=ACT_NONE, slope=0.0, group=None, precision='fp32', wgrad_s2='fp32'):
+    """batch_norm_act(conv2d(x, weight, bias, bn_stats=True), bn, act) as one autograd node (_ConvBnAct); the caller has asked
+    conv_bn_act_ok.  Parameter contract, counters and precision arguments as in conv2d and batch_norm_act."""
+    _lib.require_gpu(x)
+    if precision not in _PRECISIONS:
+        raise ValueError('conv_bn_act: unknown precision %r (one of %s)' % (precision, ', '.join(_PRECISIONS)))
+    _check_wgrad_s2('conv_bn_act', precision, wgrad_s2)
+    weight = param('conv2d', 'weight', weight, x, packed=True)
+    bias = param('conv2d', 'bias', bias, x)
+    bn_w, bn_b, bn_rm, bn_rv = bn_params('batch_norm_act', bn, x, stats=bn.track_running_stats)
+    if bn.track_running_stats and bn.num_batches_tracked is not None and not _synced(group):
+        bn.num_batches_tracked.add_(1)
+    var_mode = getattr(bn, '_ssg_var_mode', 1 if group is not None else 0)
+    pad = tuple(int(v) for v in padding) if isinstance(padding, (tuple, list)) else int(padding)
+    return _ConvBnAct.apply(x, weight, bias, bn_w, bn_b, bn_rm, bn_rv, int(stride), pad, float(bn.eps), float(bn.momentum),
+                            int(act), float(slope), int(var_mode), group, precision, wgrad_s2)
 
 
 # ----------------------------------------------------------------------------- pool / unpool / upsample
