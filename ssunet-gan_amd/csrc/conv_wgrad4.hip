@@ -13,12 +13,13 @@
 // ordered reducer of conv_wgrad.hip (bitwise reproducible, no atomics).  HBM-bound by construction.
 #include "common.h"
 #include "conv_thin.h"
+#include <type_traits>
 
 namespace {
 
 struct W4Args {
   const float* wide; const float* thin; float* ws;
-  int Cw, ldw, ldt, N, H, W, Cout, Cin;
+  int Cw, ldw, ldt, N, H, W, Cout, Cin, Cin_real;
   int groups, nz;            // 64-channel groups of the wide tensor; slabs (= workgroups per group)
   long long units_per_z;     // row segments per slice
   int segs_per_row;
@@ -122,11 +123,20 @@ __global__ __launch_bounds__(256) void wgrad4_kernel(const W4Args a) {
 }
 
 // ------------------------------------------------------------------ thin-Cin (in has 4 channels, 3x3) on the 32x32x2 MFMA
-// dw[co][tap][c] = sum_p dout[p][co] * in[p + tap][c] as a GEMM with M = 64 output channels (two fragments), N = (tap, c) = 36
-// columns (two fragments, the second holds tap 8 only) and K = pixels, two per MFMA: A = dout[p + h][co0 + m] (one dword per
-// lane: lanes 0-31 / 32-63 read one whole 128-byte line each), B = in[p + h + tap(n)][c(n)].  8 instructions per 2 pixels
-// instead of the 4x4x1 kernel's 110 per 8 (which runs at 2.2 TB/s of dout): the same slab / ordered-reduce protocol.
-__global__ __launch_bounds__(256) void wgrad32_cin_kernel(const W4Args a) {
+// dw[co][tap][c] = sum_p dout[p][co] * in[p + tap][c] as a GEMM with M = 64 output channels (two fragments), N = (tap, c) columns
+// in ONE 32-column fragment and K = pixels, two per MFMA: A = dout[p + h][co0 + m] (one dword per lane: lanes 0-31 / 32-63 read
+// one whole 128-byte line each), B = in[p + h + tap(n)][c(n)].  Two 32x32x2 MFMAs per 2 pixels:
+//   CR = 3 (the image stems, Cin_real == 3): n = tap * 3 + c, 27 columns of 32; lanes n >= 27 load nothing, the pad lane c = 3 is
+//          never read and its slab rows are not written: the reducer drops c >= Cin_real whatever they hold;
+//   CR = 4 (SPADE's hidden map): n = tap * 4 + c holds taps 0..7; tap 8 (64 channels x 4 columns) goes to one 4x4x1 MFMA per A
+//          fragment: A = the same dout register, B = in[p + h + (1,1)][lane % 4], block b = lane / 4 -> lane 4b + j, register i
+//          holds (co = 4 (b % 8) + i, c = j) of the lane half's own pixels; the two halves are added at the fold (even pixels +
+//          odd pixels, where the 32x32 columns alternate them in one chain).
+// A step is 8 pixel pairs; a step that lies whole in its 32-pixel segment skips the per-pixel tail test (a wave-uniform choice).
+// Same slab / ordered-reduce protocol as wgrad4_kernel.  Measured and dropped: tap 8 as four fmaf per lane against
+// a 16-byte load, 16 pairs per step, the A operand as one 8-byte load per lane with co = 2 * l31 + f.
+template <int CR>
+__device__ __forceinline__ void wgrad32_cin_body(const W4Args& a, float (*red)[36][64]) {
   const int lane = threadIdx.x & 63, l31 = lane & 31, h = lane >> 5;
   const int wave = threadIdx.x >> 6;
   const int zb = blockIdx.x / a.groups, cg = blockIdx.x - zb * a.groups;
@@ -136,80 +146,102 @@ __global__ __launch_bounds__(256) void wgrad32_cin_kernel(const W4Args a) {
   const auto in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.thin), 0, (int)(npix * (unsigned)a.ldt * 4u), 0x00020000);
   constexpr unsigned OOB = 0xffffffffu;
   const unsigned ldwb = (unsigned)a.ldw * 4u, ldtb = (unsigned)a.ldt * 4u;
-  // A: this lane's two output channels; B: this lane's (tap, channel) columns n = l31 and 32 + l31 (only taps 0..8 exist)
+  constexpr int NC = CR == 3 ? 27 : 32;                  // columns of the fragment in use
+  // A: this lane's two output channels; B: this lane's (tap, channel) column n = l31
   unsigned aoff[2];
 #pragma unroll
   for (int f = 0; f < 2; ++f) { const int co = cg * 64 + f * 32 + l31; aoff[f] = co < a.Cout ? (unsigned)co * 4u : OOB; }
-  const int t0 = l31 >> 2, c = l31 & 3;                  // column n = l31: tap 0..7; column 32 + l31: tap 8 for l31 < 4
+  const int t0 = l31 / CR, c = l31 - t0 * CR;
   const int dy0 = t0 / 3 - 1, dx0 = t0 % 3 - 1;
-  const bool has1 = l31 < 4;
+  const bool col_ok = l31 < NC;
 
-  f32x16 acc[2][2];
+  f32x16 acc[2];
+  f32x4 acc8[2];                                         // CR == 4: tap 8
 #pragma unroll
-  for (int f = 0; f < 2; ++f)
+  for (int f = 0; f < 2; ++f) {
 #pragma unroll
-    for (int g = 0; g < 2; ++g)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[f][g][q] = 0.f;
+    for (int q = 0; q < 16; ++q) acc[f][q] = 0.f;
+    acc8[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
 
   const int u0 = z * (int)a.units_per_z;
   const int total_units = a.N * a.H * a.segs_per_row;
   int u1 = u0 + (int)a.units_per_z; if (u1 > total_units) u1 = total_units;
-  constexpr int UP = 8;                                  // pixel pairs per inner step (16: 172 registers, 2 waves per SIMD, 3 % slower)
+  constexpr int UP = 8;                                  // pixel pairs per inner step
   for (int u = u0; u < u1; ++u) {
     const int r = u / a.segs_per_row; const int seg = u - r * a.segs_per_row;
     const int y = r % a.H, n = r / a.H;
     const int x0 = seg * SEG;
     const int x1 = x0 + SEG < a.W ? x0 + SEG : a.W;
     const unsigned rowpix = (unsigned)((n * a.H + y) * a.W);
-    const bool r0ok = (unsigned)(y + dy0) < (unsigned)a.H, r1ok = has1 && y + 1 < a.H;
+    const bool r0ok = col_ok && (unsigned)(y + dy0) < (unsigned)a.H, r8ok = y + 1 < a.H;
     const unsigned b0row = (rowpix + (unsigned)(dy0 * a.W)) * ldtb + (unsigned)c * 4u;
-    const unsigned b1row = (rowpix + (unsigned)a.W) * ldtb + (unsigned)c * 4u;
-    for (int xb = x0; xb < x1; xb += 2 * UP) {
-      float av[2][UP], bv[2][UP];
+    const unsigned b8row = (rowpix + (unsigned)a.W) * ldtb + (unsigned)(lane & 3) * 4u;
+    auto step = [&](auto full_c, const int xb) {
+      constexpr bool FULL = decltype(full_c)::value;     // all 2 * UP pixels of the step lie in the segment
+      float av[2][UP], bv[UP], b8[UP];
 #pragma unroll
       for (int k = 0; k < UP; ++k) {
         const int x = xb + 2 * k + h;
-        const bool pok = x < x1;
+        const bool pok = FULL || x < x1;
         const unsigned po = (rowpix + (unsigned)x) * ldwb;
 #pragma unroll
         for (int f = 0; f < 2; ++f)
           av[f][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(do_rs, (pok && aoff[f] != OOB) ? po + aoff[f] : OOB, 0, 0));
-        const int ix0 = x + dx0, ix1 = x + 1;
-        bv[0][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+        const int ix0 = x + dx0;
+        bv[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
             in_rs, (pok && r0ok && (unsigned)ix0 < (unsigned)a.W) ? b0row + (unsigned)ix0 * ldtb : OOB, 0, 0));
-        bv[1][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-            in_rs, (pok && r1ok && ix1 < a.W) ? b1row + (unsigned)ix1 * ldtb : OOB, 0, 0));
+        if (CR == 4)
+          b8[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+              in_rs, (pok && r8ok && x + 1 < a.W) ? b8row + (unsigned)(x + 1) * ldtb : OOB, 0, 0));
       }
 #pragma unroll
       for (int k = 0; k < UP; ++k)
 #pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-          for (int g = 0; g < 2; ++g)
-            acc[f][g] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[f][k], bv[g][k], acc[f][g], 0, 0, 0);
+        for (int f = 0; f < 2; ++f) {
+          acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[f][k], bv[k], acc[f], 0, 0, 0);
+          if (CR == 4) acc8[f] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[f][k], b8[k], acc8[f], 0, 0, 0);
+        }
+    };
+    for (int xb = x0; xb < x1; xb += 2 * UP) {
+      if (xb + 2 * UP <= x1) step(std::true_type{}, xb);
+      else step(std::false_type{}, xb);
     }
   }
-  // fold the 4 waves through LDS in wave order; D[m = co][n]: lane holds column n = l31 (+32 g), rows (q&3) + 8*(q>>2) + 4*h (+32 f)
-  __shared__ float red[4][36][64];
+  // fold the 4 waves through LDS in wave order; D[m = co][n]: lane holds column n = l31, rows (q&3) + 8*(q>>2) + 4*h (+32 f)
+  if (col_ok) {
 #pragma unroll
-  for (int f = 0; f < 2; ++f)
+    for (int f = 0; f < 2; ++f)
 #pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      const int nn = g * 32 + l31;
-      if (nn < 36) {
+      for (int q = 0; q < 16; ++q) red[wave][l31][f * 32 + (q & 3) + 8 * (q >> 2) + 4 * h] = acc[f][q];
+  }
+  if (CR == 4) {
+    // tap 8: even-pixel sums (lanes 0-31) + odd-pixel sums (lanes 32-63), rows 32..35
 #pragma unroll
-        for (int q = 0; q < 16; ++q) red[wave][nn][f * 32 + (q & 3) + 8 * (q >> 2) + 4 * h] = acc[f][g][q];
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float odd = __shfl(acc8[f][i], l31 + 32);
+        const float s8 = acc8[f][i] + odd;
+        if (h == 0) red[wave][32 + (lane & 3)][f * 32 + (l31 & ~3) + i] = s8;       // lane 4b + j, register i: (co = 4b + i, c = j)
       }
-    }
+  }
   __syncthreads();
-  float* slab = a.ws + (size_t)zb * 9 * a.Cin * a.Cout;          // [slab][row = t*Cin + c][Cout], Cin == 4: row = n
-  for (int e = threadIdx.x; e < 36 * 64; e += 256) {
+  float* slab = a.ws + (size_t)zb * 9 * a.Cin * a.Cout;          // [slab][row = t*Cin + c][Cout], Cin == 4
+  constexpr int NR = CR == 3 ? 27 : 36;
+  for (int e = threadIdx.x; e < NR * 64; e += 256) {
     const int nn = e >> 6, m = e & 63;
     const float sum = ((red[0][nn][m] + red[1][nn][m]) + red[2][nn][m]) + red[3][nn][m];
     const int co = cg * 64 + m;
-    if (co < a.Cout) slab[(size_t)nn * a.Cout + co] = sum;
+    const int row = CR == 3 ? nn + nn / 3 : nn;                  // t * 4 + c
+    if (co < a.Cout) slab[(size_t)row * a.Cout + co] = sum;
   }
+}
+
+__global__ __launch_bounds__(256) void wgrad32_cin_kernel(const W4Args a) {
+  __shared__ float red[4][36][64];
+  if (a.Cin_real == 3) wgrad32_cin_body<3>(a, red);
+  else wgrad32_cin_body<4>(a, red);
 }
 
 // ------------------------------------------------------------------ tiny: in has 4 channels AND dout has <= 8 (SPADE's 3 -> nhidden
@@ -305,7 +337,7 @@ int ssg_wgrad4_slices(const ssg_wgrad_desc* d, int kind, int* groups, long long*
 
 int ssg_wgrad4_launch(const ssg_wgrad_desc* d, int kind, hipStream_t st) {
   W4Args a;
-  a.ws = d->ws; a.N = d->N; a.H = d->H; a.W = d->W; a.Cout = d->Cout; a.Cin = d->C1;
+  a.ws = d->ws; a.N = d->N; a.H = d->H; a.W = d->W; a.Cout = d->Cout; a.Cin = d->C1; a.Cin_real = d->Cin_real;
   a.nz = ssg_wgrad4_slices(d, kind, &a.groups, &a.units_per_z, &a.segs_per_row);
   const dim3 grid((unsigned)(a.nz * a.groups)), block(256);
   if (kind == 7) {
