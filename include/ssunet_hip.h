@@ -780,6 +780,26 @@ int ssg_sw_gather_patches_d4_u8_f32(const uint8_t* img, int H, int W, const int3
 int ssg_sw_tta_reduce_f32(const float* src, int64_t slab, int ld, int K, const int32_t* codes, int B, int C, int S,
                           float* out, int ldo, void* stream);
 
+/* Confidence maps of the same pipeline.  With r_j the resized uint8 value of covering patch j at a pixel (as in
+ * ssg_sw_merge_masks_f32_u8: (uint8)(p * 255.0f), at 2x (9a + 3b + 3c + d + 8) >> 4 over the edge-clamped taps), m_j its weight
+ * and n their sum (0 -> 1), on(t) = (int)((double)(sum of m_j with r_j > t) / n * 255.0) > 127 for t in 0 .. 254 -- the mask
+ * patch_merge gives with its first-stage level at t instead of 127 -- and the score S = #{t : on(t)} in 0 .. 255.  on(t) is
+ * non-increasing in t, so on(t) <=> S > t, and S > 127 is the mask of ssg_sw_merge_masks_f32_u8 bit for bit.
+ *
+ * ssg_sw_merge_scores_f32_u8: probs, ld, P, C, S, org, org_host, weight, p_size, H, W as ssg_sw_merge_masks_f32_u8; out is
+ * [C][H][W] uint8.  thr_host == NULL: out = S.  Otherwise thr_host is a HOST array of C int32 levels in 0 .. 254 (C <= 64), read
+ * before the launch and never on the device: out[c] = S[c] > thr_host[c] ? 255 : 0, in one walk over the patches like the mask
+ * entry.  Score mode finds S by an 8-step bisection, one walk per step; exact for any number of covering patches.  Refused
+ * with SSG_EINVAL before any launch: a null pointer (thr_host excepted), P <= 0, a factor other than 1 and 2, a patch outside
+ * the image, a level outside 0 .. 254.  One thread per pixel, no atomics: deterministic.
+ *
+ * ssg_sw_score_hist_u8: scores and gt are [C][HW] uint8 (any alignment); hist is int64 [C][2][256] on the device, 8-byte aligned,
+ * zeroed by the caller before the first call: the entry ADDS, per class c and pixel, one to hist[c][gt > 127][score].  64-bit
+ * integer atomics: exact and independent of the order.  The counts of every level t follow as suffix sums over score > t. */
+int ssg_sw_merge_scores_f32_u8(const float* probs, int ld, int P, int C, int S, const int32_t* org, const int32_t* org_host,
+                               const int32_t* weight, int p_size, int H, int W, const int32_t* thr_host, uint8_t* out, void* stream);
+int ssg_sw_score_hist_u8(const uint8_t* scores, const uint8_t* gt, int C, int64_t HW, int64_t* hist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

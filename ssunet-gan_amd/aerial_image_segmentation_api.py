@@ -7,7 +7,9 @@ in, then one sigmoid kernel -- same values, no per-patch sync.  `segment_image` 
 forwards (patch cutting / resizing / normalisation, and `patch_merge`) as HIP kernels, bit for bit what the host functions
 below compute; those stay as the oracle.  With a label image it runs the ground-truth branch (`mask_convert` per patch and class,
 a second `patch_merge`, `api.py:220-236,394-406`) on the device too, and `evaluate_image` / `evaluate_images` reduce the two mask
-sets to per-class pixel counts (IoU, Dice) there, without downloading a mask.  The overlay JPGs (`save_masking*`), PNG decoding,
+sets to per-class pixel counts (IoU, Dice) there, without downloading a mask.  Not in the reference, which cuts at 127 only: the
+per-pixel confidence maps behind `patch_merge` (`patch_merge_scores`, `segment_image(..., threshold=, return_scores=)`) and the sweep
+of IoU / Dice over all 255 levels from one histogram (`evaluate_images(..., sweep=True)`).  The overlay JPGs (`save_masking*`), PNG decoding,
 non-square inference sizes and resize factors other than 1 and 2 are not covered.
 
 Host side (numpy, no cv2 / albumentations -- neither is installed here, and the package takes on no host dependency for
@@ -275,6 +277,68 @@ def patch_merge(img, masks, p_size, config, p_overlap):
     return all_class_mask
 
 
+def patch_merge_scores(img, masks, p_size, config, p_overlap):
+    """The confidence map behind `patch_merge`: per class a uint8 [H, W] score S in 0 .. 255, the number of
+    first-stage levels t in 0 .. 254 at which `patch_merge`, with `resized > t` in place of its `resized > 127` per patch and its
+    second stage unchanged, turns the pixel on.  Raising t only removes votes, so `S > t` IS that merge and `S > 127` is
+    `patch_merge` itself.  Plain numpy, the 255 merges written out: the per-patch resize is done once, the votes are summed in
+    fp64 (0.0 / 1.0 terms, exact in any order) for a block of levels at a time, and each level goes through `patch_merge`'s own
+    `(merged / div * 255).astype('uint8') > 127`.  Returns a list of num_classes arrays."""
+    img_h, img_w = img.shape[0], img.shape[1]
+    org = patch_origins(img_h, img_w, p_size, p_overlap)
+    if len(org) != len(masks):
+        raise ValueError('expected %d patches, got %d' % (len(org), len(masks)))
+    div = np.zeros((img_h, img_w))
+    for h1, w1 in org:
+        div[h1:h1 + p_size, w1:w1 + p_size] += 1.0
+    div[div == 0] = 1.0
+    block = max(1, min(255, (1 << 23) // (img_h * img_w)))             # levels merged at once: at most 64 MiB of fp64 votes
+    all_class_score = []
+    for c in range(config['num_classes']):
+        resized = [resize_u8((np.asarray(m[c]) * 255).astype('uint8'), p_size, p_size) for m in masks]
+        score = np.zeros((img_h, img_w), dtype=np.int64)
+        for t0 in range(0, 255, block):
+            levels = np.arange(t0, min(t0 + block, 255)).reshape(-1, 1, 1)
+            merged = np.zeros((levels.shape[0], img_h, img_w))
+            for (h1, w1), r in zip(org, resized):
+                merged[:, h1:h1 + p_size, w1:w1 + p_size] += (r[None] > levels)
+            full = (np.divide(merged, div) * 255).astype('uint8')
+            score += (full > 127).sum(0)
+        all_class_score.append(score.astype(np.uint8))
+    return all_class_score
+
+
+def score_hist(scores, gt):
+    """int64 [C, 2, 256]: per class c and g = (gt[c] > 127), how many pixels have each score -- the host form of
+    `ops.sw_score_hist`.  `scores`, `gt`: [C, H, W] uint8 arrays or lists of C [H, W] arrays."""
+    scores, gt = np.asarray(scores), np.asarray(gt)
+    if scores.dtype != np.uint8 or gt.dtype != np.uint8 or scores.shape != gt.shape:
+        raise TypeError('score_hist expects two uint8 arrays of one shape')
+    return np.stack([np.bincount(s.ravel().astype(np.int64) + 256 * (g.ravel() > 127), minlength=512).reshape(2, 256)
+                     for s, g in zip(scores, gt)]).astype(np.int64)
+
+
+def threshold_curves(hist):
+    """IoU and Dice of every first-stage level from a score histogram int64 [C, 2, 256] (`score_hist`, `ops.sw_score_hist`): with
+    I(t) = sum over s > t of hist[c, 1, s], P(t) = sum over s > t of hist[c, 0, s] + hist[c, 1, s] and G = sum of hist[c, 1, :],
+    `iou_curve`[c, t] = (I + 1e-5) / (P + G - I + 1e-5) and `dice_curve`[c, t] = (2 I + 1e-5) / (P + G + 1e-5) for t in 0 .. 254
+    (float64 [C, 255], the smoothing of `evaluate_images`); `best_threshold`[c] the level of the largest IoU, the lowest one on
+    ties, and `best_iou`[c] that IoU."""
+    hist = np.asarray(hist)
+    if hist.ndim != 3 or hist.shape[1:] != (2, 256):
+        raise ValueError('threshold_curves expects a [C, 2, 256] histogram, got %s' % (hist.shape,))
+    hist = hist.astype(np.int64)
+    above = np.cumsum(hist[:, :, ::-1], axis=2)[:, :, ::-1][:, :, 1:]   # [C, 2, 255]: pixels with score > t
+    i, p = above[:, 1], above[:, 0] + above[:, 1]
+    g = hist[:, 1].sum(1, keepdims=True)
+    smooth = 1e-5
+    iou = (i + smooth) / (p + g - i + smooth)
+    dice = (2 * i + smooth) / (p + g + smooth)
+    best = iou.argmax(1)                                                # first maximum: the lowest level on ties
+    return dict(iou_curve=iou, dice_curve=dice, best_threshold=[int(b) for b in best],
+                best_iou=[float(iou[c, b]) for c, b in enumerate(best)])
+
+
 # ----------------------------------------------------------------------------- the whole pipeline on the device
 def unique_origins(org):
     """(distinct origins of `org` in order of first appearance, how often each occurs).  The four corner-anchored sweeps of
@@ -287,11 +351,19 @@ def unique_origins(org):
     return list(count.keys()), list(count.values())
 
 
-def _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, who, tta=None):
+def _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, who, tta=None, threshold=None,
+                  want_scores=False, want_masks=True):
     """The device half of `segment_image` / `evaluate_image`: (prediction masks [C, H, W] uint8 on the device, ground-truth masks
-    likewise or None, probabilities, origins, weights).  Every check runs before the first upload or launch."""
+    likewise or None, probabilities, origins, weights, score maps [C, H, W] uint8 or None).  `threshold`: the masks at these
+    first-stage levels (`ops.sw_merge_scores` in mask mode) instead of `ops.sw_merge_masks`; `want_scores`: the score maps too;
+    `want_masks=False`: no prediction masks (None).  Every check runs before the first upload or launch."""
     codes = None if tta is None else ops.tta_codes(tta)
     p_size, size, overlap, classes = config['patch_size'], config['input_w'], config['patch_overlap'], config['num_classes']
+    levels = None
+    if threshold is not None:
+        levels = ops.sw_levels(threshold, classes, who)
+        if classes > 64:
+            raise ValueError('%s: thresholds for %d classes: at most 64 classes take levels' % (who, classes))
     if (config['input_h'], config['input_w']) != (size, size):
         raise NotImplementedError('non-square inference size')
     img_bgr = np.asarray(img_bgr)
@@ -326,15 +398,22 @@ def _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_b
                     x = ops.sw_gather_patches(img, org[i:i + batch_size], p_size, size, orient=k)
                     ops.sigmoid_into(model(x), stack[v, :n])
                 ops.sw_tta_reduce(stack[:, :n], codes, out=probs[i:i + batch_size])
-        masks = ops.sw_merge_masks(probs, org, weights, p_size, img_h, img_w)
+        masks = scores = None
+        if want_masks and levels is None:
+            masks = ops.sw_merge_masks(probs, org, weights, p_size, img_h, img_w)
+        elif want_masks:
+            masks = ops.sw_merge_scores(probs, org, weights, p_size, img_h, img_w, thresholds=levels)
+        if want_scores:
+            scores = ops.sw_merge_scores(probs, org, weights, p_size, img_h, img_w)
         if label_bgr is not None:                        # api.py:394-406: mask_convert per patch and class, then patch_merge
             label = torch.from_numpy(np.ascontiguousarray(label_bgr)).to(dev)
             gt = ops.sw_gather_labels(label, org, p_size, size, classes)
             gt_masks = ops.sw_merge_masks(gt, org, weights, p_size, img_h, img_w)
-    return masks, gt_masks, probs, org, weights
+    return masks, gt_masks, probs, org, weights, scores
 
 
-def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_probs=False, precision='fp32', label_bgr=None, tta=None):
+def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_probs=False, precision='fp32', label_bgr=None, tta=None,
+                  threshold=None, return_scores=False):
     """`segmentation_inference_full(model, *get_patched_input(...), config, False)[0]` for an image already in memory, with
     everything between the uint8 image and the uint8 masks on the device: the image is uploaded once, each batch of patches is
     cut, resized and normalised by `ops.sw_gather_patches`, `sigmoid(model(x))` stays on the device, `ops.sw_merge_masks` does
@@ -357,10 +436,19 @@ def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_pro
     K forwards per patch.  It composes with `dedupe`, `precision`, `label_bgr` and `return_probs`; the ground-truth masks do not
     depend on it.  Exact plumbing is what is tested; what it does to accuracy on a trained model is not measured here.  Anything
     else raises ValueError before the first upload or launch.
+    `threshold`: the operating point, not in the reference, which hard-wires 127: None (default: the statements above, nothing
+    added), an int in 0 .. 254 or a sequence of num_classes such ints.  The prediction masks are then `patch_merge` with every
+    patch thresholded at that level instead of 127 (`ops.sw_merge_scores` in mask mode; 127 gives the default
+    masks bit for bit); the second-stage level stays 127.  Bools and anything else raise ValueError before the first upload.
+    `return_scores`: also return the confidence maps, a list of num_classes uint8 [H, W] arrays of scores S in 0 .. 255
+    (`patch_merge_scores` is the host oracle): the mask at any level t is `S > t`.  They come last in the returned tuple, after the
+    `return_probs` items.  Both compose with `dedupe`, `precision`, `tta`, `label_bgr` and `return_probs`; the ground-truth masks
+    depend on neither.  Which level is best on a trained model is not measured here: there is no checkpoint.
     Not covered, as on the host path they stay with: the overlay JPGs, PNG decoding, non-square inference sizes and resize
     factors other than 1 and 2.  `evaluate_image` / `evaluate_images` turn the two mask sets into counts without a download."""
     classes = config['num_classes']
-    masks, gt_masks, probs, org, weights = _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, 'segment_image', tta)
+    masks, gt_masks, probs, org, weights, scores = _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr,
+                                                                 'segment_image', tta, threshold, bool(return_scores))
     masks = masks.cpu().numpy()
     masks = [masks[c] for c in range(classes)]
     out = (masks,)
@@ -369,42 +457,81 @@ def segment_image(model, img_bgr, config, batch_size=12, dedupe=True, return_pro
         out += ([gt_masks[c] for c in range(classes)],)
     if return_probs:
         out += (probs.cpu().contiguous().numpy(), org, weights)
+    if return_scores:
+        scores = scores.cpu().numpy()
+        out += ([scores[c] for c in range(classes)],)
     return out if len(out) > 1 else masks
 
 
-def evaluate_image(model, img_bgr, label_bgr, config, batch_size=12, dedupe=True, precision='fp32', counts=None, tta=None):
+def _hist_arg(hist, classes):
+    """`hist` of `evaluate_image`, checked before any upload: None, True, or an int64 [classes, 2, 256] device tensor."""
+    if hist is None or hist is True:
+        return hist
+    if not (isinstance(hist, torch.Tensor) and hist.is_cuda and hist.dtype == torch.int64 and tuple(hist.shape) == (classes, 2, 256)
+            and hist.is_contiguous()):
+        raise TypeError('evaluate_image: hist must be None, True or a contiguous int64 [%d, 2, 256] device tensor' % classes)
+    return hist
+
+
+def evaluate_image(model, img_bgr, label_bgr, config, batch_size=12, dedupe=True, precision='fp32', counts=None, tta=None, hist=None):
     """`segment_image(..., label_bgr=label_bgr)` with both mask sets kept on the device and reduced there by
     `ops.sw_mask_counts`: returns an int64 [num_classes, 3] DEVICE tensor of pixel counts per class -- (prediction and ground
     truth, prediction, ground truth) -- added into `counts` if such a tensor is given.  No mask is downloaded and nothing
-    synchronises; read the tensor (`.cpu()`) when the numbers are needed.  `tta`: as in `segment_image`."""
+    synchronises; read the tensor (`.cpu()`) when the numbers are needed.  `tta`: as in `segment_image`.
+    `hist`: None (default: the statements above), True, or an int64 [num_classes, 2, 256] device tensor: the score maps
+    (`ops.sw_merge_scores`) take the place of the prediction masks, and the return value is the histogram of their
+    bytes per class and ground-truth bit (`ops.sw_score_hist`), added into that tensor if one is given -- every threshold's counts
+    in one pass (`threshold_curves`).  A `counts` tensor given alongside still receives the level-127 counts (score > 127 is the
+    mask).  Still no download and no synchronisation."""
     if tta is not None:
         ops.tta_codes(tta)
     if label_bgr is None:
         raise TypeError('evaluate_image needs a label image')
-    masks, gt_masks, _, _, _ = _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, 'evaluate_image', tta)
-    return ops.sw_mask_counts(masks, gt_masks, out=counts)
+    if hist is None:
+        masks, gt_masks, _, _, _, _ = _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, 'evaluate_image', tta)
+        return ops.sw_mask_counts(masks, gt_masks, out=counts)
+    hist = _hist_arg(hist, config['num_classes'])
+    _, gt_masks, _, _, _, scores = _device_masks(model, img_bgr, config, batch_size, dedupe, precision, label_bgr, 'evaluate_image', tta,
+                                                 want_scores=True, want_masks=False)
+    if counts is not None:
+        ops.sw_mask_counts(scores, gt_masks, out=counts)               # bit 7 of a score byte is the level-127 mask
+    return ops.sw_score_hist(scores, gt_masks, out=None if hist is True else hist)
 
 
-def evaluate_images(model, pairs, config, batch_size=12, dedupe=True, precision='fp32', tta=None):
+def evaluate_images(model, pairs, config, batch_size=12, dedupe=True, precision='fp32', tta=None, sweep=False):
     """`evaluate_image` over `pairs`, an iterable of (image, label), each an HxWx3 uint8 BGR array or a path read with
     `imread_bgr`; the counts accumulate on the device and are read once at the end.  Returns a dict: `counts`, a numpy int64
     [num_classes, 3] of (intersection I, prediction P, ground truth G) pixels per class over all images, and per class the
     Python floats `iou` = (I + 1e-5) / (P + G - I + 1e-5) and `dice` = (2 I + 1e-5) / (P + G + 1e-5) -- the smoothing of
-    `metrics.iou_score`.  `tta`: as in `segment_image`."""
+    `metrics.iou_score`.  `tta`: as in `segment_image`.
+    `sweep=True`: the threshold sweep -- the score histogram (`evaluate_image(..., hist=)`) accumulates over the images beside the
+    counts and is read once; the dict then also carries `hist` (numpy int64 [num_classes, 2, 256]) and the items of
+    `threshold_curves(hist)`: `iou_curve`, `dice_curve` ([num_classes, 255], one column per first-stage level 0 .. 254),
+    `best_threshold` and `best_iou` per class.  `counts`, `iou` and `dice` stay the level-127 numbers of `sweep=False`.  What the
+    best level does for a trained model is not measured here: there is no checkpoint."""
     if tta is not None:
         ops.tta_codes(tta)
-    counts = None
+    counts = hist = None
     for image, label in pairs:
         image = imread_bgr(image) if isinstance(image, (str, os.PathLike)) else image
         label = imread_bgr(label) if isinstance(label, (str, os.PathLike)) else label
-        counts = evaluate_image(model, image, label, config, batch_size, dedupe, precision, counts, tta)
+        if sweep:
+            if counts is None:
+                counts = torch.zeros((config['num_classes'], 3), dtype=torch.int64, device=next(model.parameters()).device)
+            hist = evaluate_image(model, image, label, config, batch_size, dedupe, precision, counts, tta, True if hist is None else hist)
+        else:
+            counts = evaluate_image(model, image, label, config, batch_size, dedupe, precision, counts, tta)
     if counts is None:
         raise ValueError('evaluate_images: no (image, label) pair given')
     counts = counts.cpu().numpy()
     smooth = 1e-5
     iou = [float((i + smooth) / (p + g - i + smooth)) for i, p, g in counts.tolist()]
     dice = [float((2 * i + smooth) / (p + g + smooth)) for i, p, g in counts.tolist()]
-    return dict(counts=counts, iou=iou, dice=dice)
+    res = dict(counts=counts, iou=iou, dice=dice)
+    if sweep:
+        res['hist'] = hist.cpu().numpy()
+        res.update(threshold_curves(res['hist']))
+    return res
 
 
 def load_segmentation_models(config_file):

@@ -2311,6 +2311,75 @@ def sw_mask_counts(pred, gt, out=None):
     return out
 
 
+def sw_levels(thresholds, classes, who='sw_merge_scores'):
+    """The per-class first-stage levels of a `thresholds` request, as a list of `classes` ints: an int in 0 .. 254 stands for
+    every class, a tuple / list gives one such int per class.  Bools and anything else raise ValueError."""
+    def level(v):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 254:
+            raise ValueError('%s: threshold %r is no level (an int in 0 .. 254)' % (who, v))
+        return v
+    if isinstance(thresholds, (tuple, list)):
+        if len(thresholds) != classes:
+            raise ValueError('%s: %d thresholds for %d classes' % (who, len(thresholds), classes))
+        return [level(v) for v in thresholds]
+    return [level(thresholds)] * classes
+
+
+def sw_merge_scores(probs, origins, weights, p_size, img_h, img_w, thresholds=None):
+    """The confidence map of `patch_merge` on the device (host oracle: `patch_merge_scores`): arguments as
+    `sw_merge_masks`; returns [C, img_h, img_w] uint8 scores S -- the number of first-stage levels t in 0 .. 254 at which
+    `patch_merge`, thresholding every patch at t instead of 127, turns the pixel on; `(S > 127) * 255` is `sw_merge_masks`.
+    `thresholds`: an int level or one per class (`sw_levels`, at most 64 classes) -- then the {0, 255} masks `S[c] > level[c]`
+    come back instead, from one walk over the patches."""
+    _lib.require_gpu(probs)
+    if probs.dim() != 4 or probs.shape[2] != probs.shape[3]:
+        raise ValueError('sw_merge_scores: expected [P, C, S, S] probabilities, got %s' % (tuple(probs.shape),))
+    probs = to_nhwc(probs.detach())
+    n, c, s, _ = probs.shape
+    _sw_factor(p_size, s, 'sw_merge_scores')
+    levels = None
+    if thresholds is not None:
+        if c > 64:
+            raise ValueError('sw_merge_scores: thresholds for %d classes: at most 64 classes take levels' % c)
+        levels = (C.c_int32 * c)(*sw_levels(thresholds, c))
+    host, devo = _sw_origins(origins, probs.device)
+    wt = torch.as_tensor(weights, dtype=torch.int32, device='cpu').contiguous()
+    if host.shape[0] != n or wt.shape != (n,) or bool((wt < 0).any()):
+        raise ValueError('sw_merge_scores: %d patches need %d origins and %d non-negative weights' % (n, n, n))
+    _sw_inside(host, p_size, img_h, img_w, 'sw_merge_scores')
+    out = torch.empty((c, img_h, img_w), dtype=torch.uint8, device=probs.device)
+    wdev = wt.to(probs.device)
+    call('ssg_sw_merge_scores_f32_u8', ptr(probs), _ld(probs), n, c, s, ptr(devo), ptr(host), ptr(wdev),
+         p_size, img_h, img_w, levels, ptr(out), stream_ptr())
+    return out
+
+
+def sw_score_hist(scores, gt, out=None):
+    """Per class c and ground-truth bit g = (gt > 127), the 256-bin histogram of the score bytes: uint8 [C, H, W] (or [C, HW])
+    score maps and ground-truth masks on the device -> int64 [C, 2, 256] device tensor, hist[c, g, s] pixels.  `out`: such a
+    tensor to ADD into (and return), so that a loop accumulates over images without a host round trip.  The counts of
+    `sw_mask_counts` at any level t are suffix sums: I = hist[c, 1, t + 1:].sum(), P = hist[c, :, t + 1:].sum(), G = hist[c, 1].sum()."""
+    _lib.require_gpu(scores)
+    _lib.require_gpu(gt)
+    if scores.dtype != torch.uint8 or gt.dtype != torch.uint8 or scores.dim() < 2 or scores.shape != gt.shape:
+        raise TypeError('sw_score_hist: expected uint8 [C, H, W] scores and masks of one shape, got %s %s and %s %s'
+                        % (scores.dtype, tuple(scores.shape), gt.dtype, tuple(gt.shape)))
+    if not (scores.is_contiguous() and gt.is_contiguous()):
+        raise TypeError('sw_score_hist: the scores and the masks must be contiguous')
+    c = scores.shape[0]
+    hw = scores.numel() // c if c else 0
+    if c == 0 or hw == 0:
+        raise ValueError('sw_score_hist: empty score map %s' % (tuple(scores.shape),))
+    if out is None:
+        out = torch.zeros((c, 2, 256), dtype=torch.int64, device=scores.device)
+    else:
+        _lib.require_gpu(out)
+        if out.dtype != torch.int64 or tuple(out.shape) != (c, 2, 256) or not out.is_contiguous() or out.device != scores.device:
+            raise TypeError('sw_score_hist: out must be a contiguous int64 [%d, 2, 256] tensor on %s' % (c, scores.device))
+    call('ssg_sw_score_hist_u8', ptr(scores), ptr(gt), c, hw, ptr(out), stream_ptr())
+    return out
+
+
 class _Mul(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
