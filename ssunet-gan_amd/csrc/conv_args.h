@@ -55,6 +55,9 @@ static inline dim3 ssg_conv_tile_grid(ConvArgs& a, int TW, int TH, int BN, int s
     if (attr__ != hipSuccess) { ssg_set_error(family ": LDS attribute: %s", hipGetErrorString(attr__)); return (int)attr__; }         \
   } while (0)
 
+// conv_igemm.hip: the descriptor as the argument block, field for field (no checks; the launch sets the tile map, w_split and split-K)
+ConvArgs ssg_conv_to_args(const ssg_conv_desc* d);
+
 // conv_igemm_dma.hip: LDS-DMA pipeline for kmode 0, Cout > 32 (variant 0 = <128,128>, 1 = <256,64>)
 int ssg_conv_igemm_dma_launch(const ConvArgs& a, int variant, hipStream_t st);
 int ssg_conv_dma_variant(const ConvArgs& a, int variant);    // 0 = <128,128>, 1 = <256,64>, 2 = <128,64> (short K)

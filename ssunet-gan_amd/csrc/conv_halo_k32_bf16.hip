@@ -43,7 +43,7 @@
 // that the scratch (NI * 4 values per thread) fits the allocation.
 #include "common.h"
 #include "lds_dma.h"
-#include "conv_args.h"
+#include "conv_k32_bf16_host.h"
 #include "mfma_split.h"
 #include "conv_k32_tail.h"
 
@@ -316,11 +316,12 @@ __global__ __launch_bounds__(4 * WAVES_N * 64, 2) void conv_halo_k32_x1_kernel(c
 template <int BN, int WAVES_N>
 __global__ __launch_bounds__(4 * WAVES_N * 64, 2) void conv_halo_k32_x2_kernel(const ConvArgs a) { conv_halo_k32_bf16<BN, WAVES_N, 2>(a); }
 
-// fp32 packed [R][Kp] (kmode 0 with 9 taps: k = (chunk16 * 9 + tap) * 16 + c) -> [R / BN][chunk32 * 9 + tap][TERMS planes][BN / 16 fragments]
-// [64 lanes][16 B]: lane l of fragment j holds output channel j*16 + (l & 15), channels chunk32*32 + (l >> 4)*8 .. +7; plane 0 = the
-// value rounded to nearest even, plane 1 (two terms) = the rounded residual (split2).  One thread per (row, step, k-group).
+// fp32 packed [R][Kp] (kmode 0 with `ntaps` taps: k = (chunk16 * ntaps + tap) * 16 + c) -> [R / BN][chunk32 * ntaps + tap][TERMS planes]
+// [BN / 16 fragments][64 lanes][16 B]: lane l of fragment j holds output channel j*16 + (l & 15), channels chunk32*32 + (l >> 4)*8 .. +7;
+// plane 0 = the value rounded to nearest even, plane 1 (two terms) = the rounded residual (split2).  One thread per (row, step,
+// k-group).  Nine taps for the unit-stride and stride-2 forward convs, 1 / 2 / 4 for the parity classes of conv_s2_k32_x1.hip.
 template <int TERMS>
-__global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict__ w, int R, int Kp, int BN, unsigned char* __restrict__ out) {
+__global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict__ w, int R, int Kp, int ntaps, int BN, unsigned char* __restrict__ out) {
   const int nsteps = Kp >> 5;
   const long long total = (long long)R * nsteps * 4;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -329,9 +330,9 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict_
     const int s = (int)(t % nsteps); t /= nsteps;
     const int row = (int)t;
     const int tile = row / BN, rl = row - tile * BN;
-    const int chunk32 = s / 9, tap = s - chunk32 * 9;
+    const int chunk32 = s / ntaps, tap = s - chunk32 * ntaps;
     const int chunk16 = chunk32 * 2 + (g >> 1);
-    const float* src = w + (size_t)row * Kp + (size_t)(chunk16 * 9 + tap) * 16 + (g & 1) * 8;
+    const float* src = w + (size_t)row * Kp + (size_t)(chunk16 * ntaps + tap) * 16 + (g & 1) * 8;
     const f32x4 u = *(const f32x4*)src, v = *(const f32x4*)(src + 4);
     const int j = rl >> 4, l = (rl & 15) + 16 * g;
     unsigned char* dst = out + ((size_t)tile * nsteps + s) * BN * (64 * TERMS) + (size_t)j * 1024 + (size_t)l * 16;
@@ -366,89 +367,40 @@ int launch(const ConvArgs& a0, hipStream_t st) {
   return SSG_OK;
 }
 
+// ---- host side: the descriptor checks and the launch sequence are conv_k32_bf16_host.h's; here the choice of the kernel, and the
+// one pack launcher of the family
 constexpr const char* family(int terms) { return terms == 1 ? "bf16x1" : "bf16x2"; }
-
-// The descriptor as the kernel's argument block; false (with the reason in ssg_last_error when `why`) where the kernel does not take it.
-// `terms` names the family in the messages and sets the bytes per weight of the pack (2 * terms).
-bool conv_args(const ssg_conv_desc* d, ConvArgs& a, int terms, bool why) {
-  const char* fam = family(terms);
-#define K32_NEED(cond, fmt, ...) do { if (!(cond)) { if (why) ssg_set_error("conv %s: " fmt, fam, ##__VA_ARGS__); return false; } } while (0)
-  K32_NEED(d != nullptr, "null desc");
-  K32_NEED(d->in1 && d->w && d->out, "null pointer");
-  K32_NEED(!d->bnpart && !d->ws && !d->parity_merge && !d->in_scale && !d->in_shift && !d->bwd_x, "bnpart / ws / parity_merge / in_scale / bwd_x are not taken");
-  K32_NEED(d->ntaps == 9 && d->kmode == 0 && d->in_sy == 1 && d->in_sx == 1 && d->out_sy == 1 && d->out_sx == 1 && d->out_oy == 0 && d->out_ox == 0,
-           "the 9 taps of a unit-stride forward conv in kmode 0 only");
-  K32_NEED(d->C1 > 0 && d->C1 % 32 == 0 && d->C2 >= 0 && d->C2 % 32 == 0 && (d->C2 == 0 || d->in2), "C1=%d C2=%d must be multiples of 32", d->C1, d->C2);
-  K32_NEED(d->Cout > 0 && d->Cout % 64 == 0, "Cout=%d must be a multiple of 64", d->Cout);
-  K32_NEED(d->Kp == (d->C1 + d->C2) * 9, "Kp=%d != Cin*9", d->Kp);
-  K32_NEED(d->N > 0 && d->H > 0 && d->W > 0 && d->GH > 0 && d->GW >= 17, "empty grid or GW=%d < 17", d->GW);
-  K32_NEED(d->GH <= d->OH && d->GW <= d->OW, "pixel grid exceeds the output image");
-  K32_NEED(d->ld1 >= d->C1 && d->ld1 % 4 == 0 && (d->C2 == 0 || (d->ld2 >= d->C2 && d->ld2 % 4 == 0)) && d->ldo >= d->Cout && d->ldo % 4 == 0 &&
-           (!d->res || (d->ldr >= d->Cout && d->ldr % 4 == 0)), "pixel strides");
-  K32_NEED(ssg_aligned16(d->in1) && (d->C2 == 0 || ssg_aligned16(d->in2)) && ssg_aligned16(d->w) && ssg_aligned16(d->out) && ssg_aligned16(d->res) && ssg_aligned16(d->bias),
-           "16-B alignment");
-  K32_NEED(d->act == SSG_ACT_NONE || d->act == SSG_ACT_RELU || d->act == SSG_ACT_LRELU, "act=%d", d->act);
-  for (int t = 0; t < 9; ++t) K32_NEED(d->dy[t] >= -1 && d->dy[t] <= 1 && d->dx[t] >= -1 && d->dx[t] <= 1, "tap offset outside the 3x3 window");
-  const unsigned long long bytes = (unsigned long long)d->N * d->H * d->W * (unsigned long long)(d->ld1 > d->ld2 ? d->ld1 : d->ld2) * 4ull;
-  K32_NEED(bytes <= 0xfffffff0ull, "input beyond the 32-bit byte offsets of the buffer descriptors");
-  K32_NEED((unsigned long long)d->Cout * d->Kp * (2ull * terms) <= 0x7ffffff0ull, "weight pack beyond the 32-bit byte offsets");
-  a = ConvArgs{};
-  a.in1 = d->in1; a.in2 = d->C2 ? d->in2 : d->in1; a.bias = d->bias; a.res = d->res; a.out = d->out;
-  a.C1 = d->C1; a.C2 = d->C2; a.ld1 = d->ld1; a.ld2 = d->C2 ? d->ld2 : d->ld1;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Kp = d->Kp; a.kmode = 0;
-  a.ldr = d->ldr; a.Cout = d->Cout; a.ldo = d->ldo;
-  a.GH = d->GH; a.GW = d->GW; a.OH = d->OH; a.OW = d->OW;
-  a.in_sy = a.in_sx = a.out_sy = a.out_sx = 1;           // and out_oy = out_ox = 0: the epilogue's general pixel formula
-  a.ntaps = 9;
-  a.tap_bits = ssg_pack_taps(d->dy, d->dx, 9);
-  a.act = d->act; a.slope = d->slope;
-  a.nsteps = d->Kp / 16; a.ksplit = 1;
-  a.w32 = d->w;                                          // the slow path's fp32 weights
-  K32_NEED(ssg_conv_halo_ok(a), "the taps are not the nine of a 3x3 window");
-#undef K32_NEED
-  return true;
-}
-
-// Pack format code: 1000 * terms + BN
-int fmt_of(const ConvArgs& a, int terms) { return 1000 * terms + (a.Cout % 128 == 0 ? 128 : 64); }
-
-int fmt_or_0(const ssg_conv_desc* d, int terms) {
-  ConvArgs a;
-  return conv_args(d, a, terms, false) ? fmt_of(a, terms) : 0;
-}
 
 // 70 / 71 for one term, 90 / 91 for two: BN = 128 / 64
 int kernel_id(const ssg_conv_desc* d, int terms) {
-  const int fmt = fmt_or_0(d, terms);
+  const int fmt = ssg_k32_bf16_conv_fmt(d, K32_UNIT, family(terms), terms);
   return fmt ? (terms == 1 ? 70 : 90) + (fmt % 1000 == 128 ? 0 : 1) : SSG_EINVAL;
 }
 
 template <int TERMS>
 int run(const ssg_conv_desc* d, const void* pack, void* stream) {
-  ConvArgs a;
-  if (!conv_args(d, a, TERMS, true)) return SSG_EINVAL;
-  SSG_REQUIRE(pack != nullptr, SSG_EINVAL, "conv %s: null weight pack", family(TERMS));
-  SSG_REQUIRE(ssg_aligned16(pack), SSG_EALIGN, "conv %s: weight pack alignment", family(TERMS));
-  a.w = (const float*)pack;
-  if (a.Cout % 128 == 0) return launch<128, 2, TERMS>(a, (hipStream_t)stream);
-  return launch<64, 1, TERMS>(a, (hipStream_t)stream);
+  return ssg_k32_bf16_conv_run(d, pack, K32_UNIT, family(TERMS), TERMS, stream, [](const ConvArgs& a, hipStream_t st) {
+    return ssg_k32_bf16_bn(a.Cout) == 128 ? launch<128, 2, TERMS>(a, st) : launch<64, 1, TERMS>(a, st);
+  });
 }
 
-int64_t pack_bytes(int R, int Kp, int BN, int terms) {
+// Bytes of the pack of [R][Kp] over `ntaps` taps in format BN = 1000 * terms + column tile, or 0 where that is no pack
+int64_t pack_bytes(int R, int Kp, int ntaps, int BN, int terms) {
   const int bn = BN - 1000 * terms;
   if (bn != 64 && bn != 128) return 0;
-  if (R <= 0 || R % bn || Kp <= 0 || Kp % (32 * 9)) return 0;
+  if (ntaps <= 0 || ntaps > 9 || R <= 0 || R % bn || Kp <= 0 || Kp % (32 * ntaps)) return 0;
   return (int64_t)(R / bn) * (Kp / 32) * bn * 64 * terms;
 }
 
+// `who`: the entry point's name in the messages
 template <int TERMS>
-int pack(const float* w_packed, int R, int Kp, int BN, void* out, void* stream) {
-  SSG_REQUIRE(w_packed && out && pack_bytes(R, Kp, BN, TERMS) > 0, SSG_EINVAL, "pack %s: bad args (R=%d Kp=%d BN=%d)", family(TERMS), R, Kp, BN);
-  SSG_REQUIRE(ssg_aligned16(w_packed) && ssg_aligned16(out), SSG_EALIGN, "pack %s: 16-B alignment", family(TERMS));
+int pack(const char* who, const float* w_packed, int R, int Kp, int ntaps, int BN, void* out, void* stream) {
+  SSG_REQUIRE(w_packed && out && pack_bytes(R, Kp, ntaps, BN, TERMS) > 0, SSG_EINVAL, "pack %s: bad args (R=%d Kp=%d ntaps=%d BN=%d)", who, R, Kp, ntaps, BN);
+  SSG_REQUIRE(ssg_aligned16(w_packed) && ssg_aligned16(out), SSG_EALIGN, "pack %s: 16-B alignment", who);
   const long long total = (long long)R * (Kp >> 5) * 4;
   long long blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(pack_bf16_kernel<TERMS>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w_packed, R, Kp, BN - 1000 * TERMS, (unsigned char*)out);
+  hipLaunchKernelGGL(pack_bf16_kernel<TERMS>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w_packed, R, Kp, ntaps, BN - 1000 * TERMS, (unsigned char*)out);
   SSG_LAUNCH_CHECK();
   return SSG_OK;
 }
@@ -456,15 +408,20 @@ int pack(const float* w_packed, int R, int Kp, int BN, void* out, void* stream) 
 }  // namespace
 
 // _ok: the pack format code (BN of ssg_pack_weights_bf16x1 / _bf16x2) the launch for `d` reads, or 0 where the launch refuses `d`.
-extern "C" int ssg_conv2d_bf16x1_ok(const ssg_conv_desc* d) { return fmt_or_0(d, 1); }
+extern "C" int ssg_conv2d_bf16x1_ok(const ssg_conv_desc* d) { return ssg_k32_bf16_conv_fmt(d, K32_UNIT, "bf16x1", 1); }
 extern "C" int ssg_conv2d_bf16x1_kernel_id(const ssg_conv_desc* d) { return kernel_id(d, 1); }
 extern "C" int ssg_conv2d_bf16x1_f32(const ssg_conv_desc* d, const void* w_bf16x1, void* stream) { return run<1>(d, w_bf16x1, stream); }
-extern "C" int64_t ssg_pack_weights_bf16x1_bytes(int R, int Kp, int BN) { return pack_bytes(R, Kp, BN, 1); }
-extern "C" int ssg_pack_weights_bf16x1(const float* w_packed, int R, int Kp, int BN, void* out, void* stream) { return pack<1>(w_packed, R, Kp, BN, out, stream); }
-
-extern "C" int ssg_conv2d_bf16x2_ok(const ssg_conv_desc* d) { return fmt_or_0(d, 2); }
+extern "C" int ssg_conv2d_bf16x2_ok(const ssg_conv_desc* d) { return ssg_k32_bf16_conv_fmt(d, K32_UNIT, "bf16x2", 2); }
 extern "C" int ssg_conv2d_bf16x2_kernel_id(const ssg_conv_desc* d) { return kernel_id(d, 2); }
 extern "C" int ssg_conv2d_bf16x2_f32(const ssg_conv_desc* d, const void* w_bf16x2, void* stream) { return run<2>(d, w_bf16x2, stream); }
-extern "C" int64_t ssg_pack_weights_bf16x2_bytes(int R, int Kp, int BN) { return pack_bytes(R, Kp, BN, 2); }
-extern "C" int ssg_pack_weights_bf16x2(const float* w_packed, int R, int Kp, int BN, void* out, void* stream) { return pack<2>(w_packed, R, Kp, BN, out, stream); }
 
+// The packs: nine taps for the unit-stride and the stride-2 forward launches, the caller's tap count (1 .. 9; one term) for the
+// parity classes of conv_s2_k32_x1.hip
+extern "C" int64_t ssg_pack_weights_bf16x1_bytes(int R, int Kp, int BN) { return pack_bytes(R, Kp, 9, BN, 1); }
+extern "C" int ssg_pack_weights_bf16x1(const float* w_packed, int R, int Kp, int BN, void* out, void* stream) { return pack<1>("bf16x1", w_packed, R, Kp, 9, BN, out, stream); }
+extern "C" int64_t ssg_pack_weights_bf16x2_bytes(int R, int Kp, int BN) { return pack_bytes(R, Kp, 9, BN, 2); }
+extern "C" int ssg_pack_weights_bf16x2(const float* w_packed, int R, int Kp, int BN, void* out, void* stream) { return pack<2>("bf16x2", w_packed, R, Kp, 9, BN, out, stream); }
+extern "C" int64_t ssg_pack_weights_bf16x1_taps_bytes(int R, int Kp, int ntaps, int BN) { return pack_bytes(R, Kp, ntaps, BN, 1); }
+extern "C" int ssg_pack_weights_bf16x1_taps(const float* w_packed, int R, int Kp, int ntaps, int BN, void* out, void* stream) {
+  return pack<1>("bf16x1 taps", w_packed, R, Kp, ntaps, BN, out, stream);
+}

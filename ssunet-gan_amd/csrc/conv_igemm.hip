@@ -208,7 +208,6 @@ int pick_variant(const ssg_conv_desc* d) {
 
 // LDS-DMA pipeline (conv_igemm_dma.hip) for the dense layers; kmode 1 and the narrow outputs below stay on the
 // register-staged kernel.
-ConvArgs to_args(const ssg_conv_desc* d);
 bool uses_halo(const ConvArgs& a);
 
 bool uses_dma(const ssg_conv_desc* d) {
@@ -218,7 +217,7 @@ bool uses_dma(const ssg_conv_desc* d) {
   // level: 1024 -> 32 on 16 384 pixels = 64 tiles of the 256x32 register kernel): the 64-wide halo tile multiplies half
   // its columns by zero weights but splits K over the idle CUs (15 -> > 60 TFLOP/s)
   return d->Cout > 16 && d->ntaps == 9 && d->in_sy == 1 && d->in_sx == 1 && d->C1 + d->C2 >= 256 &&
-         (long long)d->N * d->GH * d->GW <= 32768 && uses_halo(to_args(d));
+         (long long)d->N * d->GH * d->GW <= 32768 && uses_halo(ssg_conv_to_args(d));
 }
 
 // LDS-resident halo tile (conv_igemm_halo.hip) for the 3x3 window
@@ -254,7 +253,10 @@ int validate(const ssg_conv_desc* d) {
   return SSG_OK;
 }
 
-ConvArgs to_args(const ssg_conv_desc* d) {
+}  // namespace
+
+// The descriptor as the kernels' argument block (no checks), also for the bf16 launchers (conv_k32_bf16_host.h)
+ConvArgs ssg_conv_to_args(const ssg_conv_desc* d) {
   ConvArgs a;
   a.in1 = d->in1; a.in2 = d->C2 ? d->in2 : d->in1; a.w = d->w; a.bias = d->bias; a.res = d->res; a.out = d->out;
   a.bnpart = d->bnpart;
@@ -277,6 +279,8 @@ ConvArgs to_args(const ssg_conv_desc* d) {
   a.bwd_act = d->bwd_act; a.bwd_slope = d->bwd_slope;
   return a;
 }
+
+namespace {
 
 // The kernel families in the order the dispatcher tries them: thin VALU / 4x4x1 kernels and the streaming 1x1 kernel for the
 // few-channel shapes, then on the MFMA path the split-operand kernels (bf16 terms on the bf16 matrix pipe; only with w_split) and
@@ -308,7 +312,7 @@ ConvPlan plan_conv(const ssg_conv_desc* d, bool mfma_only = false) {
     if ((p.variant = ssg_thin4_conv_kind(d))) { p.kind = KIND_THIN4; p.id = ssg_thin4_conv_id(d, p.variant); return p; }
     if ((p.variant = ssg_thin_conv_kind(d))) { p.kind = KIND_THIN; p.id = 9 + p.variant; return p; }
   }
-  const ConvArgs& a = p.a = to_args(d);
+  const ConvArgs& a = p.a = ssg_conv_to_args(d);
   const int v = p.variant = pick_variant(d);
   const bool dma = uses_dma(d), halo = uses_halo(a);
   // small grids split K over the idle CUs (fp32 halo tile, 16-byte output quads); never with bnpart (ssg_conv_halo_ksplit)

@@ -28,7 +28,7 @@
 // pieces" (plus the pixel loads issued one interval ago, where a chunk has more than one interval) covers what the interval needs.
 #include "common.h"
 #include "lds_dma.h"
-#include "conv_args.h"
+#include "conv_k32_bf16_host.h"
 #include "mfma_split.h"
 #include "conv_k32_tail.h"
 
@@ -230,32 +230,9 @@ __global__ __launch_bounds__(4 * WAVES_N * 64, 2) void conv_s2_k32_x1_kernel(con
   wait_lds_reads();
 
   // ---- the tail (conv_k32_tail.h): non-finite recompute over the NTAPS taps, then bias / activation / store.  Grid pixel (gy, gx)
-  // is output pixel (gy * out_sy + out_oy, gx * out_sx + out_ox); s2_args refuses a residual and leaves a.res null.
+  // is output pixel (gy * out_sy + out_oy, gx * out_sx + out_ox); the descriptor check refuses a residual, so a.res is null.
   ssg_k32_recompute_nonfinite<NTAPS, TH, WTM, WTN, NT>(acc, lds, tid, n, ty, tx, n0, wm, wn, kg, l15);
   ssg_k32_epilogue<TH, WTM, WTN>(a, acc, n, ty, tx, n0, wm, wn, kg, l15);
-}
-
-// ssg_pack_weights_bf16x1 for any tap count: fp32 packed [R][Kp] (kmode 0 with `ntaps` taps: k = (chunk16 * ntaps + tap) * 16 + c)
-// -> [R / BN][chunk32 * ntaps + tap][BN / 16 fragments][64 lanes][16 B].  One thread per (row, step, k-group).
-__global__ __launch_bounds__(256) void pack_bf16x1_taps_kernel(const float* __restrict__ w, int R, int Kp, int ntaps, int BN, unsigned char* __restrict__ out) {
-  const int nsteps = Kp >> 5;
-  const long long total = (long long)R * nsteps * 4;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int g = (int)(i & 3);
-    long long t = i >> 2;
-    const int s = (int)(t % nsteps); t /= nsteps;
-    const int row = (int)t;
-    const int tile = row / BN, rl = row - tile * BN;
-    const int chunk32 = s / ntaps, tap = s - chunk32 * ntaps;
-    const int chunk16 = chunk32 * 2 + (g >> 1);
-    const float* src = w + (size_t)row * Kp + (size_t)(chunk16 * ntaps + tap) * 16 + (g & 1) * 8;
-    const f32x4 u = *(const f32x4*)src, v = *(const f32x4*)(src + 4);
-    bf16x8 p;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { p[e] = (__bf16)u[e]; p[4 + e] = (__bf16)v[e]; }
-    const int j = rl >> 4, l = (rl & 15) + 16 * g;
-    *(bf16x8*)(out + ((size_t)tile * nsteps + s) * BN * 64 + (size_t)j * 1024 + (size_t)l * 16) = p;
-  }
 }
 
 template <int BN, int WAVES_N, int NTAPS, int S>
@@ -270,96 +247,34 @@ int launch(const ConvArgs& a0, hipStream_t st) {
   return SSG_OK;
 }
 
-// The descriptor as the kernel's argument block; false (with the reason in ssg_last_error when `why`) where the kernels do not take
-// it.  cls: a parity class of the input gradient (unit input stride, 1 / 2 / 4 taps at offsets {0, +1}, output stride 2), else the
-// stride-2 forward (the nine row-major taps, input stride 2, unit output stride).
-bool s2_args(const ssg_conv_desc* d, ConvArgs& a, bool cls, bool why) {
-  const char* who = cls ? "conv bf16x1 cls" : "conv bf16x1 s2";
-#define S2_NEED(cond, fmt, ...) do { if (!(cond)) { if (why) ssg_set_error("%s: " fmt, who, ##__VA_ARGS__); return false; } } while (0)
-  S2_NEED(d != nullptr, "null desc");
-  S2_NEED(d->in1 && d->w && d->out, "null pointer");
-  S2_NEED(!d->bnpart && !d->ws && !d->parity_merge && !d->in_scale && !d->in_shift && !d->bwd_x && !d->res, "bnpart / ws / parity_merge / in_scale / bwd_x / res are not taken");
-  S2_NEED(d->kmode == 0 && d->C2 == 0 && !d->in2, "kmode 0 and one input only");
-  if (cls) {
-    S2_NEED((d->ntaps == 1 || d->ntaps == 2 || d->ntaps == 4) && d->in_sy == 1 && d->in_sx == 1 && d->out_sy == 2 && d->out_sx == 2 &&
-            (d->out_oy == 0 || d->out_oy == 1) && (d->out_ox == 0 || d->out_ox == 1),
-            "1 / 2 / 4 taps at unit input stride, output stride 2 and offset 0 / 1 only");
-    for (int t = 0; t < d->ntaps; ++t) S2_NEED((d->dy[t] == 0 || d->dy[t] == 1) && (d->dx[t] == 0 || d->dx[t] == 1), "tap offset outside {0, +1}");
-    for (int t = 0; t < d->ntaps; ++t)
-      for (int u = 0; u < t; ++u) S2_NEED(d->dy[t] != d->dy[u] || d->dx[t] != d->dx[u], "a tap twice");
-  } else {
-    S2_NEED(d->ntaps == 9 && d->in_sy == 2 && d->in_sx == 2 && d->out_sy == 1 && d->out_sx == 1 && d->out_oy == 0 && d->out_ox == 0,
-            "the 9 taps of a stride-2 forward conv only");
-    for (int t = 0; t < 9; ++t) S2_NEED(d->dy[t] == t / 3 - 1 && d->dx[t] == t % 3 - 1, "the taps are not the nine row-major taps of a 3x3 pad-1 window");
-  }
-  S2_NEED(d->C1 > 0 && d->C1 % 32 == 0, "C1=%d must be a multiple of 32", d->C1);
-  S2_NEED(d->Cout > 0 && d->Cout % 64 == 0, "Cout=%d must be a multiple of 64", d->Cout);
-  S2_NEED(d->Kp == d->C1 * d->ntaps, "Kp=%d != Cin*ntaps", d->Kp);
-  S2_NEED(d->N > 0 && d->H > 0 && d->W > 0 && d->GH > 0 && d->GW >= 17, "empty grid or GW=%d < 17", d->GW);
-  S2_NEED((long long)(d->GH - 1) * d->out_sy + d->out_oy < d->OH && (long long)(d->GW - 1) * d->out_sx + d->out_ox < d->OW, "pixel grid exceeds the output image");
-  S2_NEED(d->ld1 >= d->C1 && d->ld1 % 4 == 0 && d->ldo >= d->Cout && d->ldo % 4 == 0, "pixel strides");
-  S2_NEED(ssg_aligned16(d->in1) && ssg_aligned16(d->w) && ssg_aligned16(d->out) && ssg_aligned16(d->bias), "16-B alignment");
-  S2_NEED(d->act == SSG_ACT_NONE || d->act == SSG_ACT_RELU || d->act == SSG_ACT_LRELU, "act=%d", d->act);
-  const unsigned long long bytes = (unsigned long long)d->N * d->H * d->W * (unsigned long long)d->ld1 * 4ull;
-  S2_NEED(bytes <= 0xfffffff0ull, "input beyond the 32-bit byte offsets of the buffer descriptors");
-  S2_NEED((unsigned long long)d->Cout * d->Kp * 2ull <= 0x7ffffff0ull, "weight pack beyond the 32-bit byte offsets");
-  a = ConvArgs{};
-  a.in1 = d->in1; a.in2 = d->in1; a.bias = d->bias; a.out = d->out;
-  a.C1 = d->C1; a.ld1 = d->ld1; a.ld2 = d->ld1;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Kp = d->Kp; a.kmode = 0;
-  a.Cout = d->Cout; a.ldo = d->ldo;
-  a.GH = d->GH; a.GW = d->GW; a.OH = d->OH; a.OW = d->OW;
-  a.in_sy = d->in_sy; a.in_sx = d->in_sx; a.out_sy = d->out_sy; a.out_sx = d->out_sx; a.out_oy = d->out_oy; a.out_ox = d->out_ox;
-  a.ntaps = d->ntaps;
-  a.tap_bits = ssg_pack_taps(d->dy, d->dx, d->ntaps);
-  a.act = d->act; a.slope = d->slope;
-  a.nsteps = d->Kp / 16; a.ksplit = 1;
-  a.w32 = d->w;                                          // the slow path's fp32 weights
-#undef S2_NEED
-  return true;
-}
-
-int s2_fmt(const ConvArgs& a) { return a.Cout % 128 == 0 ? 1128 : 1064; }
-
+// ---- host side: the descriptor checks and the launch sequence are conv_k32_bf16_host.h's (forms K32_S2_FWD: the nine row-major
+// taps, input stride 2, unit output stride; K32_S2_CLS: a parity class of the input gradient, unit input stride, 1 / 2 / 4 taps at
+// offsets {0, +1}, output stride 2); here the choice of the kernel
 template <int NTAPS, int S>
 int launch_bn(const ConvArgs& a, hipStream_t st) {
-  if (s2_fmt(a) == 1128) return launch<128, 2, NTAPS, S>(a, st);
+  if (ssg_k32_bf16_bn(a.Cout) == 128) return launch<128, 2, NTAPS, S>(a, st);
   return launch<64, 1, NTAPS, S>(a, st);
 }
 
-int s2_launch(const ssg_conv_desc* d, const void* pack, void* stream, bool cls) {
-  ConvArgs a;
-  if (!s2_args(d, a, cls, true)) return SSG_EINVAL;
-  SSG_REQUIRE(pack != nullptr, SSG_EINVAL, "conv bf16x1 %s: null weight pack", cls ? "cls" : "s2");
-  SSG_REQUIRE(ssg_aligned16(pack), SSG_EALIGN, "conv bf16x1 %s: weight pack alignment", cls ? "cls" : "s2");
-  a.w = (const float*)pack;
-  hipStream_t st = (hipStream_t)stream;
-  if (!cls) return launch_bn<9, 2>(a, st);
-  if (a.ntaps == 1) return launch_bn<1, 1>(a, st);
-  if (a.ntaps == 2) return launch_bn<2, 1>(a, st);
-  return launch_bn<4, 1>(a, st);
-}
+constexpr const char* FWD = "bf16x1 s2";
+constexpr const char* CLS = "bf16x1 cls";
 
 }  // namespace
 
 // Pack format code (1128 / 1064) the stride-2 forward launch for `d` reads (ssg_pack_weights_bf16x1), or 0 where it refuses `d`.
-extern "C" int ssg_conv2d_bf16x1_s2_ok(const ssg_conv_desc* d) {
-  ConvArgs a;
-  return s2_args(d, a, false, false) ? s2_fmt(a) : 0;
-}
+extern "C" int ssg_conv2d_bf16x1_s2_ok(const ssg_conv_desc* d) { return ssg_k32_bf16_conv_fmt(d, K32_S2_FWD, FWD, 1); }
 
 extern "C" int ssg_conv2d_bf16x1_s2_kernel_id(const ssg_conv_desc* d) {
   const int fmt = ssg_conv2d_bf16x1_s2_ok(d);
   return fmt == 1128 ? 73 : fmt == 1064 ? 74 : SSG_EINVAL;
 }
 
-extern "C" int ssg_conv2d_bf16x1_s2_f32(const ssg_conv_desc* d, const void* w_bf16x1, void* stream) { return s2_launch(d, w_bf16x1, stream, false); }
+extern "C" int ssg_conv2d_bf16x1_s2_f32(const ssg_conv_desc* d, const void* w_bf16x1, void* stream) {
+  return ssg_k32_bf16_conv_run(d, w_bf16x1, K32_S2_FWD, FWD, 1, stream, [](const ConvArgs& a, hipStream_t st) { return launch_bn<9, 2>(a, st); });
+}
 
 // The same for one parity class of the input gradient (pack: ssg_pack_weights_bf16x1_taps with d->ntaps).
-extern "C" int ssg_conv2d_bf16x1_cls_ok(const ssg_conv_desc* d) {
-  ConvArgs a;
-  return s2_args(d, a, true, false) ? s2_fmt(a) : 0;
-}
+extern "C" int ssg_conv2d_bf16x1_cls_ok(const ssg_conv_desc* d) { return ssg_k32_bf16_conv_fmt(d, K32_S2_CLS, CLS, 1); }
 
 extern "C" int ssg_conv2d_bf16x1_cls_kernel_id(const ssg_conv_desc* d) {
   const int fmt = ssg_conv2d_bf16x1_cls_ok(d);
@@ -367,22 +282,10 @@ extern "C" int ssg_conv2d_bf16x1_cls_kernel_id(const ssg_conv_desc* d) {
   return 75 + (d->ntaps == 1 ? 0 : d->ntaps == 2 ? 2 : 4) + (fmt == 1128 ? 0 : 1);
 }
 
-extern "C" int ssg_conv2d_bf16x1_cls_f32(const ssg_conv_desc* d, const void* w_bf16x1, void* stream) { return s2_launch(d, w_bf16x1, stream, true); }
-
-extern "C" int64_t ssg_pack_weights_bf16x1_taps_bytes(int R, int Kp, int ntaps, int BN) {
-  if (BN != 1064 && BN != 1128) return 0;
-  const int bn = BN - 1000;
-  if (ntaps <= 0 || ntaps > 9 || R <= 0 || R % bn || Kp <= 0 || Kp % (32 * ntaps)) return 0;
-  return (int64_t)(R / bn) * (Kp / 32) * bn * 64;
-}
-
-extern "C" int ssg_pack_weights_bf16x1_taps(const float* w_packed, int R, int Kp, int ntaps, int BN, void* out, void* stream) {
-  SSG_REQUIRE(w_packed && out && ssg_pack_weights_bf16x1_taps_bytes(R, Kp, ntaps, BN) > 0, SSG_EINVAL, "pack bf16x1 taps: bad args (R=%d Kp=%d ntaps=%d BN=%d)", R, Kp, ntaps, BN);
-  SSG_REQUIRE(ssg_aligned16(w_packed) && ssg_aligned16(out), SSG_EALIGN, "pack bf16x1 taps: 16-B alignment");
-  const long long total = (long long)R * (Kp >> 5) * 4;
-  long long blocks = (total + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(pack_bf16x1_taps_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w_packed, R, Kp, ntaps, BN - 1000, (unsigned char*)out);
-  SSG_LAUNCH_CHECK();
-  return SSG_OK;
+extern "C" int ssg_conv2d_bf16x1_cls_f32(const ssg_conv_desc* d, const void* w_bf16x1, void* stream) {
+  return ssg_k32_bf16_conv_run(d, w_bf16x1, K32_S2_CLS, CLS, 1, stream, [](const ConvArgs& a, hipStream_t st) {
+    if (a.ntaps == 1) return launch_bn<1, 1>(a, st);
+    if (a.ntaps == 2) return launch_bn<2, 1>(a, st);
+    return launch_bn<4, 1>(a, st);
+  });
 }

@@ -219,7 +219,7 @@ Plan make_plan(const ssg_wgrad_desc* d) {
     // Slabs: a slab is one workgroup's accumulation chain, so its length bounds the fp32 rounding error -- at most 128 rows (4096
     // pixels, the slab of wgrad_halo_x3 at the bench sizes; in-register totals that cut the chain instead cost 72 registers and
     // 10 % of the kernel: DESIGN.md 3.10) and at least 8 rows (256 pixels, the shortest slab of the fp32 kernels); within that,
-    // the count that leaves the fewest CUs idle in the last wave of 256 workgroups (one workgroup per CU)
+    // the count that leaves the fewest CUs idle in the last wave of 256 workgroups (one workgroup per CU): ssg_wgrad_slabs
     // ... and never longer than the chain the 16-pixel-step kernels would use on this shape (their planner below: ~1024 workgroups,
     // >= 16 steps per slab), so that the rounding error of the two families stays equal on every shape, not only at the bench sizes
     long long max_rows = 128;
@@ -234,18 +234,8 @@ Plan make_plan(const ssg_wgrad_desc* d) {
       if (chain_px / 32 < max_rows) max_rows = chain_px / 32;
       if (max_rows < 8) max_rows = 8;
     }
-    const long long lo = (steps + max_rows - 1) / max_rows;
-    long long hi = steps / 8;
-    if (hi < lo) hi = lo;
-    long long best = lo; double beff = 0;
-    for (long long sp = lo; sp <= hi && sp <= lo + 1024; ++sp) {
-      const long long wg = sp * tiles;
-      const double eff = (double)wg / (256.0 * ((wg + 255) / 256));
-      if (eff > beff + 1e-9) { beff = eff; best = sp; }
-      if (eff >= 0.97 && wg >= 256) break;
-    }
-    p.steps_per_split = (int)((steps + best - 1) / best);
-    p.splits = (int)((steps + p.steps_per_split - 1) / p.steps_per_split);
+    const WgSlabs s = ssg_wgrad_slabs(steps, tiles, 8, max_rows);
+    p.steps_per_split = s.steps_per_split; p.splits = s.splits;
     return p;
   }
   long long want = 1024 / ((long long)p.mt * p.nt);       // ~4 workgroups per CU overall (2048: +0.4 % slab traffic time)
@@ -285,22 +275,6 @@ bool in_affine_ok(const ssg_wgrad_desc* d, const Plan& p) {
   return p.kind == WG_K32;
 }
 
-// the kernels' argument block of a validated descriptor under plan p
-WgArgs wgrad_args(const ssg_wgrad_desc* d, const Plan& p) {
-  WgArgs a;
-  a.in1 = d->in1; a.in2 = d->C2 ? d->in2 : d->in1; a.dout = d->dout; a.ws = d->ws;
-  a.C1 = d->C1; a.C2 = d->C2; a.ld1 = d->ld1; a.ld2 = d->C2 ? d->ld2 : d->ld1;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cout = d->Cout; a.ldd = d->ldd; a.GH = d->GH; a.GW = d->GW;
-  a.in_sy = d->in_sy; a.in_sx = d->in_sx; a.ntaps = d->ntaps;
-  a.tap_bits = ssg_pack_taps(d->dy, d->dx, d->ntaps);
-  a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.in_act = d->in_act; a.in_slope = d->in_slope;
-  a.M = d->ntaps * (d->C1 + d->C2);
-  a.Ptot = (long long)d->N * d->GH * d->GW;
-  a.steps_per_split = p.steps_per_split;
-  a.xcd_swizzle = 0;
-  return a;
-}
-
 __global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restrict__ w, int O, int I, int KH, int KW,
                                                            int transpose, int ntaps, unsigned long long kpos_bits,
                                                            int kmode, int Cred_pad, int Kp, int R, float* __restrict__ out,
@@ -330,6 +304,22 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restri
 
 }  // namespace
 
+// the kernels' argument block of a validated descriptor whose plan gives a slab `steps_per_split` K-steps
+WgArgs ssg_wgrad_args(const ssg_wgrad_desc* d, int steps_per_split) {
+  WgArgs a;
+  a.in1 = d->in1; a.in2 = d->C2 ? d->in2 : d->in1; a.dout = d->dout; a.ws = d->ws;
+  a.C1 = d->C1; a.C2 = d->C2; a.ld1 = d->ld1; a.ld2 = d->C2 ? d->ld2 : d->ld1;
+  a.N = d->N; a.H = d->H; a.W = d->W; a.Cout = d->Cout; a.ldd = d->ldd; a.GH = d->GH; a.GW = d->GW;
+  a.in_sy = d->in_sy; a.in_sx = d->in_sx; a.ntaps = d->ntaps;
+  a.tap_bits = ssg_pack_taps(d->dy, d->dx, d->ntaps);
+  a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.in_act = d->in_act; a.in_slope = d->in_slope;
+  a.M = d->ntaps * (d->C1 + d->C2);
+  a.Ptot = (long long)d->N * d->GH * d->GW;
+  a.steps_per_split = steps_per_split;
+  a.xcd_swizzle = 0;
+  return a;
+}
+
 extern "C" int64_t ssg_conv2d_wgrad_workspace_bytes(const ssg_wgrad_desc* d) {
   return d ? workspace_bytes(d, make_plan(d)) : 0;
 }
@@ -347,7 +337,7 @@ extern "C" int ssg_conv2d_wgrad_f32(const ssg_wgrad_desc* d, void* stream) {
   SSG_REQUIRE(!d->in_scale || (d->in_shift && in_affine_ok(d, p)), SSG_EINVAL,
               "wgrad: in_scale on a descriptor whose kernel has no fused input transform (ssg_conv2d_wgrad_in_affine_ok == 0)");
   hipStream_t st = (hipStream_t)stream;
-  WgArgs a = wgrad_args(d, p);
+  WgArgs a = ssg_wgrad_args(d, p.steps_per_split);
   if (p.kind == WG_4) {
     rc = ssg_wgrad4_launch(d, p.variant, st);
     if (rc != SSG_OK) return rc;
@@ -367,28 +357,18 @@ extern "C" int ssg_conv2d_wgrad_f32(const ssg_wgrad_desc* d, void* stream) {
     }
     SSG_LAUNCH_CHECK();
   }
-  RedArgs r;
-  r.ws = d->ws; r.dw = d->dw_oihw; r.splits = p.splits; r.M = a.M; r.Cout = d->Cout; r.Cin = d->C1 + d->C2;
-  r.Cin_real = d->Cin_real; r.KH = d->KH; r.KW = d->KW; r.ntaps = d->ntaps;
-  for (int t = 0; t < SSG_MAX_TAPS; ++t) { r.ky[t] = t < d->ntaps ? d->ky[t] : 0; r.kx[t] = t < d->ntaps ? d->kx[t] : 0; }
-  const long long tot = (long long)a.M * d->Cout;
-  // many slabs over few elements (the thin layers): 32 split-lanes keep the serial chains short
-  if (p.splits >= 256 && tot <= 32 * 1024)
-    hipLaunchKernelGGL(wgrad_reduce_kernel<32>, dim3((unsigned)ssg_cdiv(tot, 32)), dim3(1024), 0, st, r);
-  else
-    hipLaunchKernelGGL(wgrad_reduce_kernel<8>, dim3((unsigned)ssg_cdiv(tot, 32)), dim3(256), 0, st, r);
-  SSG_LAUNCH_CHECK();
-  return SSG_OK;
+  return ssg_wgrad_reduce_launch(d, p.splits, st);
 }
 
-// The ordered second stage alone, for a launcher outside this file (conv_wgrad_k32_bf16.hip): `splits` slabs [9 * Cin][Cout] in d->ws
-// -> d->dw_oihw, wgrad_reduce_kernel as ssg_conv2d_wgrad_f32 launches it.
+// The ordered second stage, also for the launchers outside this file (conv_k32_bf16_host.h): `splits` slabs [ntaps * Cin][Cout] in
+// d->ws -> d->dw_oihw.
 int ssg_wgrad_reduce_launch(const ssg_wgrad_desc* d, int splits, hipStream_t st) {
   RedArgs r;
   r.ws = d->ws; r.dw = d->dw_oihw; r.splits = splits; r.M = d->ntaps * (d->C1 + d->C2); r.Cout = d->Cout; r.Cin = d->C1 + d->C2;
   r.Cin_real = d->Cin_real; r.KH = d->KH; r.KW = d->KW; r.ntaps = d->ntaps;
   for (int t = 0; t < SSG_MAX_TAPS; ++t) { r.ky[t] = t < d->ntaps ? d->ky[t] : 0; r.kx[t] = t < d->ntaps ? d->kx[t] : 0; }
   const long long tot = (long long)r.M * d->Cout;
+  // many slabs over few elements (the thin layers): 32 split-lanes keep the serial chains short
   if (splits >= 256 && tot <= 32 * 1024)
     hipLaunchKernelGGL(wgrad_reduce_kernel<32>, dim3((unsigned)ssg_cdiv(tot, 32)), dim3(1024), 0, st, r);
   else
@@ -445,5 +425,5 @@ extern "C" int ssg_wgrad_dma_body(const ssg_wgrad_desc* d) {
   if (!d || validate(d) != SSG_OK) return 0;
   const Plan p = make_plan(d);
   if (p.kind != WG_MFMA || !wgrad_uses_dma(p.variant) || !(d->flags & 1)) return 0;
-  return ssg_wgrad_dma_split_body(wgrad_args(d, p), p.variant, (long long)p.mt * p.nt * p.splits);
+  return ssg_wgrad_dma_split_body(ssg_wgrad_args(d, p.steps_per_split), p.variant, (long long)p.mt * p.nt * p.splits);
 }

@@ -35,5 +35,28 @@ bool ssg_wgrad_k32_ok(const ssg_wgrad_desc* d);
 long long ssg_wgrad_k32_steps(const ssg_wgrad_desc* d);
 int ssg_wgrad_k32_launch(const WgArgs& a, dim3 grid, hipStream_t st);
 
-// conv_wgrad.hip: the ordered slab reduce (wgrad_reduce_kernel) for conv_wgrad_k32_bf16.hip, which plans and launches on its own
+// conv_wgrad.hip: the kernels' argument block of a validated descriptor, and the ordered slab reduce (wgrad_reduce_kernel), also for
+// the bf16 launchers (conv_k32_bf16_host.h), which plan and launch on their own
+WgArgs ssg_wgrad_args(const ssg_wgrad_desc* d, int steps_per_split);
 int ssg_wgrad_reduce_launch(const ssg_wgrad_desc* d, int splits, hipStream_t st);
+
+// Slab count of the kernels whose K-step is one image row of a 32-pixel column strip (wgrad_k32 and the bf16 family).  A slab is one
+// workgroup's accumulation chain of min_rows .. max_rows K-steps; within that, the count that leaves the fewest CUs idle in the last
+// wave of 256 workgroups (one workgroup per CU): the first best of at most 1025 counts, the scan ending early at 97 % of a full wave.
+struct WgSlabs { int splits, steps_per_split; };
+inline WgSlabs ssg_wgrad_slabs(long long steps, long long tiles, long long min_rows, long long max_rows) {
+  const long long lo = (steps + max_rows - 1) / max_rows;
+  long long hi = steps / min_rows;
+  if (hi < lo) hi = lo;
+  long long best = lo; double beff = 0;
+  for (long long sp = lo; sp <= hi && sp <= lo + 1024; ++sp) {
+    const long long wg = sp * tiles;
+    const double eff = (double)wg / (256.0 * ((wg + 255) / 256));
+    if (eff > beff + 1e-9) { beff = eff; best = sp; }
+    if (eff >= 0.97 && wg >= 256) break;
+  }
+  WgSlabs s;
+  s.steps_per_split = (int)((steps + best - 1) / best);
+  s.splits = (int)((steps + s.steps_per_split - 1) / s.steps_per_split);
+  return s;
+}

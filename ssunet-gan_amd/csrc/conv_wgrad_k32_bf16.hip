@@ -33,7 +33,7 @@
 // holds a non-finite accumulator.
 #include "common.h"
 #include "lds_dma.h"
-#include "conv_wgrad_args.h"
+#include "conv_k32_bf16_host.h"
 #include "mfma_split.h"
 #include "conv_slow.h"
 
@@ -44,16 +44,14 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
-constexpr int KP = 32;                     // pixels per K-step
+constexpr int KP = WG_BF16_KP;             // pixels per K-step
 constexpr int WPX = 36;                    // pixel rows per x slot (34 used: window columns gx0 - 1 .. gx0 + 32)
 constexpr int XSLOT = WPX * 128;           // bytes
 constexpr int XSLOTS = 8;
 constexpr int XIMG = XSLOTS * XSLOT;
 constexpr int DHALF = KP * 128;            // one dy row, 64 output channels
 constexpr int DSLOTS = 4;
-constexpr int CB = 64;
-constexpr int MAX_ROWS = 128;              // longest accumulation chain of a slab, in K-steps (4096 pixels: wgrad_k32's)
-constexpr int MIN_ROWS = 8;
+constexpr int CB = WG_BF16_CB;
 constexpr int lds_bytes_of(int NJ, int TERMS) { return TERMS * (XIMG + DSLOTS * (NJ / 2) * DHALF); }      // one plane of each image per term
 
 // 16-byte chunk c (0..7) of pixel row p sits at chunk position c ^ sw(p)
@@ -171,7 +169,7 @@ __device__ __forceinline__ void wgrad_k32_bf16(const WgArgs a) {
     }
   }
 
-  // One accumulator sums a whole slab: the planner keeps a slab at <= MAX_ROWS K-steps (4096 pixels), as for wgrad_k32_kernel.
+  // One accumulator sums a whole slab: the planner keeps a slab at <= WG_BF16_MAX_ROWS K-steps (4096 pixels), as for wgrad_k32_kernel.
   f32x4 acc[9][NJ];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
@@ -301,53 +299,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_k32_x1_kernel(const WgArgs a) { 
 template <int NJ>
 __global__ __launch_bounds__(512, 1) void wgrad_k32_x2_kernel(const WgArgs a) { wgrad_k32_bf16<NJ, 2>(a); }
 
-// ---- host side, the same for both term counts: the shapes, the slab plan and the workspace do not depend on TERMS
-struct Plan { int nj, mt, nt, splits, steps_per_split; };
-
-// The shape test alone (no pointers): what ssg_conv2d_wgrad_bf16x1_ok and ssg_conv2d_wgrad_bf16x2_ok answer.
-bool shape_ok(const ssg_wgrad_desc* d) {
-  if (!d || d->in_scale || d->in_shift) return false;
-  if (d->ntaps != 9 || d->KH != 3 || d->KW != 3 || d->in_sy != 1 || d->in_sx != 1) return false;
-  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->GH != d->H || d->GW != d->W) return false;
-  for (int t = 0; t < 9; ++t)
-    if (d->dy[t] != t / 3 - 1 || d->dx[t] != t % 3 - 1 || d->ky[t] != t / 3 || d->kx[t] != t % 3) return false;
-  if (d->C1 <= 0 || d->C1 % 64 || d->C2 < 0 || d->C2 % 64 || d->Cout <= 0 || d->Cout % 64 || d->GW < 17) return false;
-  if (d->Cin_real != d->C1 + d->C2) return false;
-  if ((d->ld1 & 3) || d->ld1 < d->C1 || (d->C2 && ((d->ld2 & 3) || d->ld2 < d->C2)) || (d->ldd & 3) || d->ldd < d->Cout) return false;
-  const unsigned long long xb = (unsigned long long)d->N * d->H * d->W * (unsigned long long)(d->ld1 > d->ld2 ? d->ld1 : d->ld2) * 4ull;
-  const unsigned long long db = (unsigned long long)d->N * d->GH * d->GW * (unsigned long long)d->ldd * 4ull;
-  return xb <= 0xfffffff0ull && db <= 0xfffffff0ull;
-}
-
-// Slabs: a slab is one workgroup's accumulation chain, MIN_ROWS..MAX_ROWS K-steps; within that, the count that leaves the fewest
-// CUs idle in the last wave of 256 workgroups (one workgroup per CU), as wgrad_k32's plan.
-Plan plan(const ssg_wgrad_desc* d) {
-  Plan p;
-  p.nj = d->Cout % 128 == 0 ? 4 : 2;
-  p.mt = (d->C1 + d->C2) / CB; p.nt = d->Cout / (32 * p.nj);
-  const long long steps = (long long)d->N * ((d->GW + KP - 1) / KP) * d->GH;
-  const long long tiles = (long long)p.mt * p.nt;
-  const long long lo = (steps + MAX_ROWS - 1) / MAX_ROWS;
-  long long hi = steps / MIN_ROWS;
-  if (hi < lo) hi = lo;
-  long long best = lo; double beff = 0;
-  for (long long sp = lo; sp <= hi && sp <= lo + 1024; ++sp) {
-    const long long wg = sp * tiles;
-    const double eff = (double)wg / (256.0 * ((wg + 255) / 256));
-    if (eff > beff + 1e-9) { beff = eff; best = sp; }
-    if (eff >= 0.97 && wg >= 256) break;
-  }
-  p.steps_per_split = (int)((steps + best - 1) / best);
-  p.splits = (int)((steps + p.steps_per_split - 1) / p.steps_per_split);
-  return p;
-}
-
-int64_t ws_bytes(const ssg_wgrad_desc* d, const Plan& p) {
-  return (int64_t)p.splits * 9 * (d->C1 + d->C2) * d->Cout * (int64_t)sizeof(float);
-}
-
-int64_t ws_bytes_or_0(const ssg_wgrad_desc* d) { return shape_ok(d) ? ws_bytes(d, plan(d)) : 0; }
-
+// ---- host side: conv_k32_bf16_host.h, the same for both term counts (the shapes, the slab plan and the workspace do not depend on
+// TERMS); here only the choice of the kernel
 template <int NJ, int TERMS>
 int launch(const WgArgs& a, dim3 grid, hipStream_t st) {
   constexpr int lds_bytes = lds_bytes_of(NJ, TERMS);
@@ -362,42 +315,21 @@ int launch(const WgArgs& a, dim3 grid, hipStream_t st) {
   return SSG_OK;
 }
 
-// Validate, launch the slabs, reduce them in order.  `fam`: the precision's name in the messages.
 template <int TERMS>
 int run(const ssg_wgrad_desc* d, void* stream) {
-  const char* fam = TERMS == 1 ? "bf16x1" : "bf16x2";
-  SSG_REQUIRE(d && d->in1 && d->dout && d->dw_oihw && d->ws, SSG_EINVAL, "wgrad %s: null pointer", fam);
-  SSG_REQUIRE(d->C2 == 0 || d->in2, SSG_EINVAL, "wgrad %s: C2 > 0 needs in2", fam);
-  SSG_REQUIRE(shape_ok(d), SSG_EINVAL,
-              "wgrad %s: not the 3x3 stride-1 pad-1 weight gradient with C1 %% 64 == C2 %% 64 == Cout %% 64 == 0, GW >= 17, 32-bit byte offsets "
-              "and no in_scale (C1=%d C2=%d Cout=%d GW=%d ntaps=%d stride=%d)", fam, d->C1, d->C2, d->Cout, d->GW, d->ntaps, d->in_sy);
-  SSG_REQUIRE(ssg_aligned16(d->in1) && ssg_aligned16(d->in2) && ssg_aligned16(d->dout) && ssg_aligned16(d->ws), SSG_EALIGN, "wgrad %s: alignment", fam);
-  const Plan p = plan(d);
-  SSG_REQUIRE(d->ws_bytes >= ws_bytes(d, p), SSG_EINVAL, "wgrad %s: workspace too small", fam);
-  hipStream_t st = (hipStream_t)stream;
-  WgArgs a{};
-  a.in1 = d->in1; a.in2 = d->C2 ? d->in2 : d->in1; a.dout = d->dout; a.ws = d->ws;
-  a.C1 = d->C1; a.C2 = d->C2; a.ld1 = d->ld1; a.ld2 = d->C2 ? d->ld2 : d->ld1;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cout = d->Cout; a.ldd = d->ldd; a.GH = d->GH; a.GW = d->GW;
-  a.in_sy = a.in_sx = 1; a.ntaps = 9;
-  a.tap_bits = ssg_pack_taps(d->dy, d->dx, 9);
-  a.M = 9 * (d->C1 + d->C2);
-  a.Ptot = (long long)d->N * d->GH * d->GW;
-  a.steps_per_split = p.steps_per_split;
-  const dim3 grid((unsigned)p.mt, (unsigned)p.nt, (unsigned)p.splits);
-  const int rc = p.nj == 4 ? launch<4, TERMS>(a, grid, st) : launch<2, TERMS>(a, grid, st);
-  if (rc != SSG_OK) return rc;
-  return ssg_wgrad_reduce_launch(d, p.splits, st);
+  return ssg_wgrad_bf16_run(d, 1, TERMS == 1 ? "bf16x1" : "bf16x2", stream, [](int nj, const WgArgs& a, dim3 grid, hipStream_t st) {
+    return nj == 4 ? launch<4, TERMS>(a, grid, st) : launch<2, TERMS>(a, grid, st);
+  });
 }
 
 }  // namespace
 
-extern "C" int ssg_conv2d_wgrad_bf16x1_ok(const ssg_wgrad_desc* d) { return shape_ok(d) ? 1 : 0; }
-extern "C" int ssg_conv2d_wgrad_bf16x1_kernel_id(const ssg_wgrad_desc* d) { return shape_ok(d) ? 72 : SSG_EINVAL; }
-extern "C" int64_t ssg_conv2d_wgrad_bf16x1_workspace_bytes(const ssg_wgrad_desc* d) { return ws_bytes_or_0(d); }
+extern "C" int ssg_conv2d_wgrad_bf16x1_ok(const ssg_wgrad_desc* d) { return ssg_wgrad_bf16_shape_ok(d, 1) ? 1 : 0; }
+extern "C" int ssg_conv2d_wgrad_bf16x1_kernel_id(const ssg_wgrad_desc* d) { return ssg_wgrad_bf16_shape_ok(d, 1) ? 72 : SSG_EINVAL; }
+extern "C" int64_t ssg_conv2d_wgrad_bf16x1_workspace_bytes(const ssg_wgrad_desc* d) { return ssg_wgrad_bf16_ws_bytes(d, 1); }
 extern "C" int ssg_conv2d_wgrad_bf16x1_f32(const ssg_wgrad_desc* d, void* stream) { return run<1>(d, stream); }
 
-extern "C" int ssg_conv2d_wgrad_bf16x2_ok(const ssg_wgrad_desc* d) { return shape_ok(d) ? 1 : 0; }
-extern "C" int ssg_conv2d_wgrad_bf16x2_kernel_id(const ssg_wgrad_desc* d) { return shape_ok(d) ? 92 : SSG_EINVAL; }
-extern "C" int64_t ssg_conv2d_wgrad_bf16x2_workspace_bytes(const ssg_wgrad_desc* d) { return ws_bytes_or_0(d); }
+extern "C" int ssg_conv2d_wgrad_bf16x2_ok(const ssg_wgrad_desc* d) { return ssg_wgrad_bf16_shape_ok(d, 1) ? 1 : 0; }
+extern "C" int ssg_conv2d_wgrad_bf16x2_kernel_id(const ssg_wgrad_desc* d) { return ssg_wgrad_bf16_shape_ok(d, 1) ? 92 : SSG_EINVAL; }
+extern "C" int64_t ssg_conv2d_wgrad_bf16x2_workspace_bytes(const ssg_wgrad_desc* d) { return ssg_wgrad_bf16_ws_bytes(d, 1); }
 extern "C" int ssg_conv2d_wgrad_bf16x2_f32(const ssg_wgrad_desc* d, void* stream) { return run<2>(d, stream); }

@@ -8,9 +8,11 @@ in tests/test_s2_bf16x1_ref.py):
   (c) bound     |y - fp64 on the operands as given| <= (2^-8 + 2^-18) conv(|x|, |w|) + 2 x that kernel's max error, elementwise."""
 import ctypes
 
+import numpy as np
 import pytest
 import torch
 
+import bf16x2_ref as X2
 import s2_bf16x1_ref as R
 import layout_probe as LP
 
@@ -118,6 +120,58 @@ def test_every_new_instantiation_ran(pkg, dev):
     for name in R.DGRAD_CASES:
         seen |= set(_run_dgrad(pkg, dev, name)['labels'])
     assert seen == set(pkg.ops._X1_CLS_LABELS.values()), seen
+
+
+def _bf16_bits(t):
+    """bf16 (round to nearest even, R.rb) bit patterns of an fp32 tensor, as a numpy uint16 array."""
+    return (R.rb(t).numpy().view(np.uint32) >> 16).astype(np.uint16)
+
+
+def _pack_x1_taps_ref(wp, ntaps, bn):
+    """ssg_pack_weights_bf16x1_taps restated (bf16x2_ref.pack_x2 with one plane and any tap count).  wp: fp32 [R, Kp] in kmode 0 with
+    `ntaps` taps (k = (chunk16 * ntaps + tap) * 16 + c) -> uint16 [R / bn][Kp / 32 steps = chunk32 * ntaps + tap][bn / 16 fragments]
+    [64 lanes][8 values]: lane l of fragment j holds row j * 16 + (l & 15), channels chunk32 * 32 + (l >> 4) * 8 .. + 7."""
+    rows, kp = wp.shape
+    bits = _bf16_bits(wp)
+    out = np.zeros((rows // bn, kp // 32, bn // 16, 64, 8), dtype=np.uint16)
+    for s in range(kp // 32):
+        chunk32, tap = divmod(s, ntaps)
+        for g in range(4):
+            k0 = ((chunk32 * 2 + (g >> 1)) * ntaps + tap) * 16 + (g & 1) * 8
+            out[:, s, :, 16 * g:16 * g + 16, :] = bits[:, k0:k0 + 8].reshape(rows // bn, bn // 16, 16, 8)
+    return out
+
+
+@pytest.mark.parametrize('rows,cin', [(64, 32), (64, 64), (128, 32), (128, 64)])
+def test_pack_bytes_match_the_restatement_for_every_tap_count(pkg, dev, rows, cin):
+    """The one pack kernel behind ssg_pack_weights_bf16x1 / _bf16x1_taps / _bf16x2, bitwise: both column tiles, one and two 32-channel
+    chunks, every tap count, values whose bf16 rounding is a tie (to even: down and up, both signs)."""
+    ops, lib = pkg.ops, pkg._lib
+    bn = 128 if rows % 128 == 0 else 64
+
+    def packed(entry, wp, fmt, nbytes, *taps):
+        assert lib.call(entry + '_bytes', rows, wp.shape[1], *taps, fmt) == nbytes
+        buf = torch.zeros(nbytes // 2, dtype=torch.int16, device=dev)
+        wd = wp.to(dev)
+        lib.call(entry, wd.data_ptr(), rows, wp.shape[1], *taps, fmt, ops.ptr(buf), ops.stream_ptr())
+        return buf.cpu().numpy().view(np.uint16)
+
+    g = torch.Generator().manual_seed(77 + rows + cin)
+    for ntaps in (1, 2, 4, 9):
+        kp = cin * ntaps
+        wp = torch.randn(rows, kp, generator=g)
+        ties = torch.tensor([1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8, -(1 + 2.0 ** -8), -(1 + 3 * 2.0 ** -8), 2.0 ** -20 * (1 + 5 * 2.0 ** -8)])
+        wp.view(-1)[torch.randperm(rows * kp, generator=g)[:4 * len(ties)]] = ties.repeat(4)
+        assert ((wp.view(torch.int32) & 0xffff) == 0x8000).sum() >= 4 * len(ties)   # halfway between two bf16 values
+        want = _pack_x1_taps_ref(wp, ntaps, bn)
+        got = packed('ssg_pack_weights_bf16x1_taps', wp, 1000 + bn, rows * kp * 2, ntaps)
+        assert np.array_equal(got.reshape(want.shape), want), ntaps
+        if ntaps == 9:
+            assert np.array_equal(packed('ssg_pack_weights_bf16x1', wp, 1000 + bn, rows * kp * 2), got)
+            want2 = X2.pack_x2(wp.numpy(), bn)
+            assert np.array_equal(want2[:, :, 0], want)                              # plane 0 of two terms is the one-term pack
+            got2 = packed('ssg_pack_weights_bf16x2', wp, 2000 + bn, rows * kp * 4)
+            assert np.array_equal(got2.reshape(want2.shape), want2)
 
 
 def test_channel_slices_of_wider_tensors(pkg, dev):

@@ -49,7 +49,7 @@ def kernel_id(c):
 
 
 def plan(c):
-    """s2_plan of conv_wgrad_s2_k32_x1.hip: the rule of plan() in conv_wgrad_k32_bf16.hip (8 .. 128 K-steps per slab, fewest idle CUs in the last wave) on
+    """ssg_wgrad_bf16_plan of csrc/conv_k32_bf16_host.h at stride 2 (8 .. 128 K-steps per slab, fewest idle CUs in the last wave) on
     steps = N * ceil(GW / 32) * GH of the OUTPUT grid -- wgrad_x1_ref.plan reads GH / GW from wgrad_ref.geom, which are the output's at
     stride 2.  (nj, mt, nt, steps, steps_per_split, splits)."""
     return xr.plan(c)

@@ -52,7 +52,7 @@ def case(name):
 
 
 def plan(c):
-    """plan() of conv_wgrad_k32_bf16.hip restated: (nj, mt, nt, steps, steps_per_split, splits)."""
+    """ssg_wgrad_bf16_plan of csrc/conv_k32_bf16_host.h restated: (nj, mt, nt, steps, steps_per_split, splits)."""
     g = wr.geom(c)
     nj = 4 if c.Cout % 128 == 0 else 2
     mt, nt = g.Cin // 64, c.Cout // (32 * nj)
