@@ -800,6 +800,29 @@ int ssg_sw_merge_scores_f32_u8(const float* probs, int ld, int P, int C, int S, 
                                const int32_t* weight, int p_size, int H, int W, const int32_t* thr_host, uint8_t* out, void* stream);
 int ssg_sw_score_hist_u8(const uint8_t* scores, const uint8_t* gt, int C, int64_t HW, int64_t* hist, void* stream);
 
+/* ------------------------------------------------------------------ training augmentation (HBM-bound)
+ * ssg_augment_batch_u8_f32: one launch turns a batch of uint8 source tiles into the network's input and target.  img is
+ * [N][H][W][3] uint8 (B, G, R), mask [N][H][W][C] uint8, C in 1 .. 8, any alignment.  params is the DEVICE table the kernel
+ * reads, int32 [N][16]; params_host the caller's HOST copy of the same values, which the entry point checks before it launches;
+ * lut is uint8 [N][256] on the device.  A row holds m0 .. m5, flags, dh, ds, dv and six zeros.
+ *   Geometry: m0 .. m5 are 16.16 fixed point; output pixel (i, j) (row, column) reads the source at sx = m0 j + m1 i + m2,
+ *   sy = m3 j + m4 i + m5 in int64 (pixel-index coordinates: the half-pixel shifts are folded into m2 and m5).  Image: bilinear,
+ *   x0 = sx >> 16, fx = (sx >> 8) & 255, likewise y; the taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) weigh
+ *   (256 - fx)(256 - fy), fx (256 - fy), (256 - fx) fy, fx fy; a tap outside the source is the byte border[c] and is never read;
+ *   v = (sum + 2^15) >> 16.  Mask: nearest, (sx + 2^15) >> 16 and (sy + 2^15) >> 16, 0 outside.
+ *   Colour: if flags bit 0 is set, (B, G, R) -> integer H in 0 .. 179, S, V in 0 .. 255 (round-half-up divisions),
+ *   H = (H + dh) mod 180, S = clip(S + ds), V = clip(V + dv), and back in integers; then every byte indexes the sample's lut.
+ *   Output: out_img is [N, 3, out_h, out_w] fp32 NHWC with ld = 4, ((float)byte - mean[c]) * rdenom[c] (two fp32 roundings;
+ *   mean / rdenom as in ssg_sw_gather_patches_u8_f32, no further / 255), pad lane 0; out_tgt is [N, C, out_h, out_w] fp32 NHWC
+ *   with ld = C rounded up to 4, (float)mask byte, pad lanes 0.  Both 16-byte aligned.
+ * tests/augment_ref.py states all of it in numpy; the entry is that bit for bit.  Refused with SSG_EINVAL before any launch:
+ * a null pointer, N, H, W, out_h or out_w <= 0, C outside 1 .. 8, a border value outside 0 .. 255, a params_host row with a flag
+ * bit other than bit 0, |dh| > 179, |ds| or |dv| > 255, or a map whose coordinates would leave int64.  One writer per element. */
+int ssg_augment_batch_u8_f32(const uint8_t* img, const uint8_t* mask, int N, int H, int W, int C, const int32_t* params,
+                             const int32_t* params_host, const uint8_t* lut, int out_h, int out_w,
+                             int border0, int border1, int border2, float mean0, float mean1, float mean2,
+                             float rdenom0, float rdenom1, float rdenom2, float* out_img, float* out_tgt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,5 +14,6 @@ from . import ops, bf16, blocks, archs, normalization, models_seg_gan, losses, m
 from . import xresidualblock, spectral_norm, batchnorm, efficientnet_pytorch  # noqa: F401  (unwired per-op rows A9-A12)
 from . import train  # noqa: F401  (stage-1 trainer)
 from . import aerial_image_segmentation_api  # noqa: F401  (sliding-window inference)
+from . import augment  # noqa: F401  (device-side training augmentation)
 
 __version__ = '0.1.0'

@@ -218,6 +218,7 @@ SIGNATURES = {
     'ssg_sw_tta_reduce_f32': [_P, _L, _I, _I, _P, _I, _I, _I, _P, _I, _P],
     'ssg_sw_merge_scores_f32_u8': [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P],
     'ssg_sw_score_hist_u8': [_P, _P, _I, _L, _P, _P],
+    'ssg_augment_batch_u8_f32': [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P],
     'ssg_spade_modulate_dgamma_sums_f32': [_P, _I, _P, _I, _L, _I, _P, _I, _P, _P, _P],
     'ssg_spade_dgrad_modulate_ok': [C.POINTER(ConvDesc)],
     'ssg_spade_dgrad_modulate_f32': [C.POINTER(ConvDesc), _P, _I, _P, _I, _P],

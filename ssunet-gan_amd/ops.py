@@ -2380,6 +2380,56 @@ def sw_score_hist(scores, gt, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- training augmentation (csrc/augment.hip)
+AUG_ROW = 16             # int32 entries of a parameter row: m0 .. m5 (16.16), flags, dh, ds, dv, six zeros (augment.py builds them)
+
+
+def augment_batch(img_u8, mask_u8, params, luts, out_h, out_w, border=(0, 0, 0), out=None):
+    """Network input and target of a training batch from uint8 tiles on the device, in one launch:
+    `img_u8` [N, H, W, 3] (B, G, R) and `mask_u8` [N, H, W, C] (C in 1 .. 8), contiguous uint8 on one HIP device; `params` the
+    HOST int32 [N, 16] table and `luts` the HOST uint8 [N, 256] tables of `augment.sample_params` (numpy arrays or CPU tensors).
+    Per sample: one affine resampling (bilinear image taps, `border` bytes outside the source; nearest masks, 0 outside), the
+    integer HSV shift where the row's flag asks for it, the brightness / contrast table, Normalize.  Returns
+    ([N, 3, out_h, out_w], [N, C, out_h, out_w]) fp32 NHWC with zero pad lanes -- `new_nhwc` tensors, which the generator and
+    `seg_loss` take as they are; `out`: such a pair to write into.  tests/augment_ref.py is the definition, bit for bit.
+    Anything else raises before a launch."""
+    _lib.require_gpu(img_u8)
+    _lib.require_gpu(mask_u8)
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[3] != 3 or not img_u8.is_contiguous():
+        raise TypeError('augment_batch: expected contiguous [N, H, W, 3] uint8 images, got %s %s' % (img_u8.dtype, tuple(img_u8.shape)))
+    if mask_u8.dtype != torch.uint8 or mask_u8.dim() != 4 or mask_u8.shape[:3] != img_u8.shape[:3] or not mask_u8.is_contiguous():
+        raise TypeError('augment_batch: expected contiguous [N, H, W, C] uint8 masks beside %s images, got %s %s'
+                        % (tuple(img_u8.shape), mask_u8.dtype, tuple(mask_u8.shape)))
+    if mask_u8.device != img_u8.device:
+        raise TypeError('augment_batch: images on %s, masks on %s' % (img_u8.device, mask_u8.device))
+    n, h, w, c = mask_u8.shape
+    if n == 0 or h == 0 or w == 0 or not 1 <= c <= 8:
+        raise ValueError('augment_batch: %d samples of %d x %d with %d mask channels (1 .. 8 are built)' % (n, h, w, c))
+    if out_h <= 0 or out_w <= 0:
+        raise ValueError('augment_batch: output %d x %d' % (out_h, out_w))
+    host = torch.as_tensor(params).contiguous()
+    tabs = torch.as_tensor(luts).contiguous()
+    if host.is_cuda or host.dtype != torch.int32 or tuple(host.shape) != (n, AUG_ROW):
+        raise TypeError('augment_batch: params must be a host int32 [%d, %d] table, got %s %s' % (n, AUG_ROW, host.dtype, tuple(host.shape)))
+    if tabs.is_cuda or tabs.dtype != torch.uint8 or tuple(tabs.shape) != (n, 256):
+        raise TypeError('augment_batch: luts must be host uint8 [%d, 256] tables, got %s %s' % (n, tabs.dtype, tuple(tabs.shape)))
+    border = tuple(int(b) for b in border)
+    if len(border) != 3 or not all(0 <= b <= 255 for b in border):
+        raise ValueError('augment_batch: border %r is no byte triple' % (border,))
+    dev = img_u8.device
+    if out is None:
+        inp, tgt = new_nhwc(n, 3, out_h, out_w, dev), new_nhwc(n, c, out_h, out_w, dev)
+    else:
+        inp, tgt = out
+        for t, ch in ((inp, 3), (tgt, c)):
+            if tuple(t.shape) != (n, ch, out_h, out_w) or t.device != dev or nhwc_ld(t) != pad4(ch):
+                raise TypeError('augment_batch: out must be new_nhwc(%d, %d, %d, %d) tensors on %s' % (n, ch, out_h, out_w, dev))
+    dev_params, dev_tabs = host.to(dev), tabs.to(dev)          # named: both must outlive the launch's enqueue
+    call('ssg_augment_batch_u8_f32', ptr(img_u8), ptr(mask_u8), n, h, w, c, ptr(dev_params), ptr(host), ptr(dev_tabs),
+         out_h, out_w, *(list(border) + _sw_norm_consts() + [ptr(inp), ptr(tgt), stream_ptr()]))
+    return inp, tgt
+
+
 class _Mul(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):

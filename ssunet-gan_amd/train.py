@@ -42,9 +42,12 @@ def train(epoch, config, train_loader, model, criterion, optimizer, cnn_optimize
     sync = dp.grad_sync(model)
     params = [p for p in model.parameters()]
     precision = config.get('precision', 'fp32')                              # 'bf16x1' / 'bf16x2': ops.train_precision around forward and backward
+    augment = config.get('device_augment')                                   # an augment.DeviceAugment: the loader then yields raw tiles
     for ori_img, input, target, targets, _ in train_loader:
         input = input.cuda(non_blocking=True)
         target = target.cuda(non_blocking=True)
+        if augment is not None:
+            input, target = augment(input, target)
         with ops.train_precision(precision):
             loss, iou, dice = _loss_and_metrics(config, model, criterion, input, target, num_class)
         clamp_parameters_(params, clip)                                      # :111-112
@@ -79,10 +82,14 @@ def validate(config, val_loader, model, criterion):
     avg_meters = {'loss': AverageMeter(), 'iou': AverageMeter(), 'dice': AverageMeter()}
     model.eval()
     num_class = int(config['num_classes'])
+    augment = config.get('device_augment')
+    augment = augment.validation() if augment is not None else None    # its train=False twin: the reference's val_transform
     with torch.no_grad():
         for ori_img, input, target, targets, _ in val_loader:
             input = input.cuda(non_blocking=True)
             target = target.cuda(non_blocking=True)
+            if augment is not None:
+                input, target = augment(input, target)
             loss, iou, dice = _loss_and_metrics(config, model, criterion, input, target, num_class)
             n = input.size(0)
             avg_meters['loss'].update(loss, n)

@@ -169,10 +169,13 @@ def train(epoch, config, train_loader, generator, discriminator, criterion, adve
     print('generator learning rate {:d}: {:f}'.format(epoch, lr_val))
     num_class = int(config['num_classes'])
     sync_g, sync_d = dp.grad_syncs(generator, discriminator)
+    augment = config.get('device_augment')          # an augment.DeviceAugment: the loader then yields raw tiles
 
     for ori_img, input, target, targets, _ in train_loader:
         input = input.cuda(non_blocking=True)
         target = target.cuda(non_blocking=True)
+        if augment is not None:
+            input, target = augment(input, target)
         loss, iou, dice, _, _, _ = gan_step(input, target, generator, discriminator, criterion,
                                              adversarial_loss_criterion, content_loss_criterion, optimizer_g, optimizer_d,
                                              num_class, sync_g, sync_d, precision=config.get('precision', 'fp32'),
@@ -191,10 +194,14 @@ def validate(config, val_loader, generator, criterion):
     """train_seg_gan.py:253-294."""
     avg_meters = {'loss': AverageMeter(), 'iou': AverageMeter(), 'dice': AverageMeter()}
     generator.eval()
+    augment = config.get('device_augment')
+    augment = augment.validation() if augment is not None else None    # its train=False twin: the reference's val_transform
     with torch.no_grad():
         for ori_img, input, target, targets, _ in val_loader:
             input = input.cuda(non_blocking=True)
             target = target.cuda(non_blocking=True)
+            if augment is not None:
+                input, target = augment(input, target)
             output = ops.nan_to_zero_(generator(input))
             res = ops.seg_loss(output, target, metric_first_channel=1)
             loss = res[0] if isinstance(criterion, BCEDiceLoss) else criterion(output, target)
